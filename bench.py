@@ -14,11 +14,18 @@ generated on the device (gym_traffic/workload.py); per-GPU work is fixed as N gr
 envs are sharded by id with no collective in the step; for N > 1 a snapshot of (obs, reward, done)
 is gathered to rank 0 over RCCL every 10 ticks on a side stream (cfg3).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ONE region of K ticks and prints
+the line (ms_per_step = that region / K).  Everything else it measures runs only with --full:
+  repeats       --repeats (default 5) fenced regions of K ticks, the line's value being their median;
   roofline      dominant kernel (k_move): algorithmic bytes per launch / its mean duration measured
-                with HIP events on the launch stream inside the timed region, against 8 TB/s;
+                with HIP events on the launch stream in a second pass over K ticks, against 8 TB/s;
+  agent steps   fused 10-tick agent decisions timed on a second handle;
   cpu_baseline  the CPU oracle (a port of the reference's algorithm, oracle/idm_oracle.c) timed on
                 this host's cores on a bounded sample of the same workload (N = 1, rank 0 only).
+
+--dump-outputs DIR writes, right after the timed region, what its last tick left to a caller of
+the step as DIR/<name>.npy (see dump_outputs).  The workload is a pure function of the arguments,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -195,6 +202,46 @@ def roofline(a, c, eng, E, prof, prof_updates, chunk, dt, updates):
                         "range is not split over two streams while a launch is timed)"}
 
 
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: at most this much in all (split evenly over the ranks)
+DUMP_SEED = 0              # the seeded sample of envs a dump holds when the whole batch does not fit
+
+
+def dump_outputs(eng, out_dir, budget, suffix=""):
+    """What the last timed tick left to a caller of the step, for a fixed, seeded sample of the envs (all of them when
+    they fit in `budget` bytes; otherwise the sorted draw of RandomState(DUMP_SEED) without replacement):
+      obs [n, obs_len], done [n], leading / lastcar [n, R]     float64 (the device's int32 / uint8, exact)
+      rewards [n, I], x / v [n, R, C] by ring slot              float32, slots that hold no car set to 0
+    Returns the number of envs written."""
+    import numpy as np
+    import torch
+    E, R, C, I = eng.E, eng.R, eng.C, eng.I
+    per_env = 8 * (eng.obs_len + 1 + 2 * R) + 4 * (I + 2 * R * C)
+    n = max(1, min(E, budget // per_env))
+    idx = np.arange(E) if n == E else np.sort(np.random.RandomState(DUMP_SEED).choice(E, n, replace=False))
+    sel = torch.as_tensor(idx, dtype=torch.long, device=eng.device)
+    ring = eng.xv.index_select(0, sel).cpu().numpy()             # [n, R, C, 2] (a transposed handle exports first)
+    eng.drop_staging()
+    leading = eng.leading.index_select(0, sel).cpu().numpy()
+    lastcar = eng.lastcar.index_select(0, sel).cpu().numpy()
+    # live slots of a ring: wrap(leading + 1) .. lastcar, none when leading == lastcar
+    s = np.arange(C)[None, None, :]
+    ld, lc = leading[..., None], lastcar[..., None]
+    live = np.where(ld <= lc, (s > ld) & (s <= lc), (s > ld) | ((s >= 1) & (s <= lc))) & (ld != lc)
+    arrays = {
+        "obs": eng.obs.index_select(0, sel).cpu().numpy().astype(np.float64),
+        "rewards": eng.rewards.index_select(0, sel).cpu().numpy().astype(np.float32),
+        "done": eng.done.index_select(0, sel).cpu().numpy().astype(np.float64),
+        "leading": leading.astype(np.float64),
+        "lastcar": lastcar.astype(np.float64),
+        "x": np.where(live, ring[..., 0], np.float32(0)).astype(np.float32),
+        "v": np.where(live, ring[..., 1], np.float32(0)).astype(np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+    return n
+
+
 def numpy_baseline(name, budget_s=8.0):
     """SURVEY 8d's second CPU leg: the same tick as batched NumPy array arithmetic on ONE core (oracle/numpy_env.py)."""
     from oracle.numpy_env import time_config
@@ -314,10 +361,19 @@ def main():
                     help="N = 1 with everything a rank of an N > 1 run does: an RCCL process group (of one rank), the "
                          "snapshot + gather every %d ticks, barriers and reductions" % GATHER_EVERY)
     ap.add_argument("--no-numpy-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps ticks each (fenced); the line reports their median and the spread")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: 5 timed regions (--repeats), the roofline pass, the "
+                         "fused agent decisions and the CPU baselines (a plain run times one region of --steps ticks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last tick computed as DIR/<name>.npy (float32 / "
+                         "float64, at most %d MB; a seeded sample of the envs when the batch is larger)"
+                         % (DUMP_BYTES // 10 ** 6))
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps ticks each (fenced); the line reports their median and the spread "
+                         "(default: 1, with --full 5)")
     ap.add_argument("--no-agent-steps", action="store_true",
-                    help="skip the measurement of fused agent decisions (profile runs: only the timed ticks' launches)")
+                    help="with --full: skip the measurement of fused agent decisions (profile runs: only the timed "
+                         "ticks' launches)")
     ap.add_argument("--settle", type=int, default=None,
                     help="untimed ticks run right after the prefill, as part of the workload's setup and before the W "
                          "warm-up steps (default: the workload's, gym_traffic/workload.py SETTLE_TICKS; 0 = none)")
@@ -329,6 +385,8 @@ def main():
                          "runs no kernel and measures nothing")
     ap.add_argument("--selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a, sys.argv[1:]))
     if a.selftest_launcher:
@@ -426,24 +484,28 @@ def main():
     pair_ticks = (eng.pair_ticks() - pair_ticks0) // len(regions)
     split_ticks = (eng.split_ticks() - split_ticks0) // len(regions)
 
-    # Roofline pass: the SAME K ticks again, now with HIP events on the launch stream around every launch of the
-    # kernel that moves the cars (tfx_profile).  While it is timed a launch owns the chip: the handle does not
-    # split the env range over two streams in this pass (tfx_split_ticks), so the duration is the kernel's own.
-    eng.profile(a.steps)
-    eng.reset_counters()
-    fence()
-    run(a.steps)
-    fence()
-    prof = eng.profile_read()
-    prof_updates = eng.vehicle_updates()
-    eng.profile(0)
+    if a.dump_outputs:
+        dump_outputs(eng, a.dump_outputs, DUMP_BYTES // world, "_rank%d" % rank if rank else "")
 
-    # Agent decisions, MEASURED: the fused 10-tick decision (Repeater + Remi, tfx_agent_step) under the same rules, on
-    # a second handle brought to the state the first timed region started from (prefill, settle ticks, warm-up): late in a
-    # long run the benchmark's entry roads run full, and an env that overflows in the first tick of a decision stands
-    # still for the rest of it (`if done: break`) - which would time decisions that do nothing
+    # Roofline pass (--full): the SAME K ticks again, now with HIP events on the launch stream around every launch of
+    # the kernel that moves the cars (tfx_profile).  While it is timed a launch owns the chip: the handle does not
+    # split the env range over two streams in this pass (tfx_split_ticks), so the duration is the kernel's own.
+    if a.full:
+        eng.profile(a.steps)
+        eng.reset_counters()
+        fence()
+        run(a.steps)
+        fence()
+        prof = eng.profile_read()
+        prof_updates = eng.vehicle_updates()
+        eng.profile(0)
+
+    # Agent decisions, MEASURED (--full): the fused 10-tick decision (Repeater + Remi, tfx_agent_step) under the same
+    # rules, on a second handle brought to the state the first timed region started from (prefill, settle ticks,
+    # warm-up): late in a long run the benchmark's entry roads run full, and an env that overflows in the first tick of a
+    # decision stands still for the rest of it (`if done: break`) - which would time decisions that do nothing
     n_dec, dt_agent, agent_done = 0, 0.0, 0
-    if not a.no_agent_steps:
+    if a.full and not a.no_agent_steps:
         eng2 = wl.setup_engine(a.config, device=device, envs=E, env_id_offset=rank * E)
         for n in [50] * (settle // 50) + [settle % 50, a.warmup]:
             if n:
@@ -511,15 +573,16 @@ def main():
             "ticks_in_two_tick_passes": pair_ticks,
             "ticks_split_over_two_streams": split_ticks,
             "ticks_per_call": min(chunk, K),
-            "roofline": roofline(a, c, eng, E, prof, prof_updates, chunk, dt_max, updates),
         }
+        if a.full:
+            out["roofline"] = roofline(a, c, eng, E, prof, prof_updates, chunk, dt_max, updates)
         if dist_on:
             # what a scaling curve needs beside the aggregate: the ranks' own times for the median region
             out["per_rank_ms_per_step"] = {"max": dt_max / K * 1e3, "min": float(t_min[mid].item()) / K * 1e3}
             out["t_max_over_t_min"] = dt_max / max(1e-12, float(t_min[mid].item()))
             out["rccl_ranks_seen"] = dist.get_world_size() if not rehearsal else 0
             out["gather_ms_per_snapshot"] = gather.ms_per_snapshot() if gather is not None else None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.config)
             if not a.no_numpy_baseline:
                 out["cpu_baseline"]["numpy_batched_one_core"] = numpy_baseline(a.config)

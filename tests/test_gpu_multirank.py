@@ -73,7 +73,7 @@ def test_bench_launches_its_ranks_rehearsal(ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["TFX_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "20", "--warmup", "5",
-                        "--envs", "256", "--repeats", "3"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--envs", "256", "--repeats", "3", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        universal_newlines=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

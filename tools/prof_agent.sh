@@ -6,7 +6,7 @@ O=$R/gpurun_out/${1:-prof_agent}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/agent -o p --output-format csv -- python3 $R/tools/bench_agent_step.py > $O/agent.log 2>&1
-rocprofv3 --kernel-trace --stats -d $O/plain -o p --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --call-ticks 10 --repeats 2 --no-cpu-baseline > $O/plain.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/plain -o p --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --call-ticks 10 --repeats 2 --no-cpu-baseline > $O/plain.log 2>&1
 cd $R
 for k in agent plain; do echo "== $k"; f=$(find $O/$k -name '*kernel_stats.csv' | head -1); python3 - "$f" <<'PY'
 import csv, sys

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/timeline_${1:-step}; mkdir -p $O; cd /tmp; e
 if [ "${1:-step}" = agent ]; then
   rocprofv3 --kernel-trace -d $O/kt -o p --output-format csv -- python3 $R/tools/bench_agent_step.py cfg2 > $O/kt.log 2>&1
 else
-  rocprofv3 --kernel-trace -d $O/kt -o p --output-format csv -- python3 $R/bench.py --steps 40 --warmup 10 --no-cpu-baseline > $O/kt.log 2>&1
+  rocprofv3 --kernel-trace -d $O/kt -o p --output-format csv -- python3 $R/bench.py --full --steps 40 --warmup 10 --no-cpu-baseline > $O/kt.log 2>&1
 fi
 cd $R; O=$O python3 - <<'PY'
 import csv,glob,os

@@ -3,7 +3,7 @@
 #   bash tools/sweep_segments.sh > gpurun_out/segments.txt      (run through gpurun)
 cd $GRAFT_REPO_ROOT
 c4() { python3 tools/c4_loop.py $1 2>&1 | grep closed | sed 's/, [0-9]* cars.*//'; }
-b2() { python3 bench.py --config $1 --envs $2 --steps 100 --warmup 10 --repeats 3 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%s x %s: %.1f us per tick (%s), fused 10-tick decision %.1f us' % ('$1', '$2', d['ms_per_step']*1e3, d['roofline']['kernel'], d['agent_decision_ms']*1e3))"; }
+b2() { python3 bench.py --full --config $1 --envs $2 --steps 100 --warmup 10 --repeats 3 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%s x %s: %.1f us per tick (%s), fused 10-tick decision %.1f us' % ('$1', '$2', d['ms_per_step']*1e3, d['roofline']['kernel'], d['agent_decision_ms']*1e3))"; }
 echo "# cfg4 closed loop (64x64, 128-car rings, on-device Poisson + greedy, empty start), env-ticks/s; S = segments per tile"
 for E in 1 2 4 8 16; do
   echo "default:            $(c4 $E)"

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-sweep_tail}; mkdir -p $O; cd $R
 run() { # label, env...
   local label=$1; shift
-  env "$@" python3 bench.py --steps 100 --warmup 20 --repeats 3 --no-cpu-baseline > $O/$label.json 2> $O/$label.err
+  env "$@" python3 bench.py --full --steps 100 --warmup 20 --repeats 3 --no-cpu-baseline > $O/$label.json 2> $O/$label.err
   python3 - "$O/$label.json" "$label" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-sweep}; shift; mkdir -p $O; cd $R
 for n in "$@"; do
   lib=$R/traffic-env_amd/lib/exp/libtfx_$n.so
   [ "$n" = base ] && lib=$R/traffic-env_amd/lib/libtfx_hip.so
-  TFX_LIB=$lib python3 bench.py --steps 100 --warmup 20 --repeats 3 --no-cpu-baseline > $O/$n.json 2> $O/$n.err
+  TFX_LIB=$lib python3 bench.py --full --steps 100 --warmup 20 --repeats 3 --no-cpu-baseline > $O/$n.json 2> $O/$n.err
   python3 - "$O/$n.json" "$n" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
