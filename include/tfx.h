@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TFX_ABI_VERSION 11
+#define TFX_ABI_VERSION 12
 #define TFX_KP 2 /* popped cars carried per road per tick on the parallel path; more -> exact serial path */
 #define TFX_MAX_ARCH 64 /* rows of the archetype table (traffic_env.py:35-43 ships one); a power of two */
 
@@ -166,20 +166,34 @@ int tfx_set_spawns(tfx_handle h, int32_t mode, const int32_t *dev, int32_t perio
  * round(Exp(1/cars_per_tick)) ticks between cars, each car on a uniformly drawn entry road; Philox
  * streams keyed by (seed, global env id).  `cdf` (host pointer, n_cdf entries) holds
  * P(gap <= k) * 2^32 for k = 0.. (the last entry must be 0xFFFFFFFF); gym_traffic/devrng.py builds it
- * and mirrors the stream on the host. */
+ * and mirrors the stream on the host.
+ *
+ * Heterogeneous handles (tfx_config.n_archetypes): the stream also draws the archetype-table row of every car
+ * (`archetypes[random.randint(n)]`, traffic_env.py:164) and binds those rows as the spawn rows (in place of any
+ * tfx_set_spawn_archetypes buffer).  Rule 1: take car j (0-based) that the stream puts on entry index ej of global env
+ * g in a tick, and let s be the number of cars the stream has put on that entry road of that env before this tick
+ * (every car made counts, overflowed ones included; an env that stands still in an agent step makes none).  Its row is
+ *     row = (u0 * n_archetypes) >> 32,  u = philox4x32(ctr = {s + j, g, TAG_ARCH, ej}, key = seed)
+ * with TAG_ARCH = 0x41524348 (the gap and road draws use 0x47415021 / 0x524F4144 and keep their indices: the counts
+ * are those of a single-archetype handle with the same seed).  Rows are stored for j < S = C - 2 only: no road takes
+ * more cars in one tick (add_car, traffic_env.py:97-114; the cars past it overflow), so no car past it reaches a road.
+ * The stream's rows stay bound until a later tfx_set_spawns (which unbinds them: cars get row 0 unless a
+ * tfx_set_spawn_archetypes buffer is bound after it), tfx_set_spawn_archetypes (its buffer replaces them) or
+ * tfx_set_regular / tfx_set_poisson. */
 int tfx_set_poisson(tfx_handle h, double cars_per_tick, uint64_t seed, const uint32_t *cdf, int32_t n_cdf);
 /* On-device form of the reference's `regular` generator (traffic_env.py:167-176): with cars_per_tick =
  * cars_per_sec * rate, `burst` = ceil(cars_per_tick) cars in every tick i of the env's generator with
  * i % every == 0, `every` = round(1 / cars_per_tick) (Python's round: half to even; every == 0 means every tick) -
  * the caller passes the two integers; each car on a uniformly drawn entry road (rand.choice(entrypoints), :280) from the
  * Philox stream keyed by (seed, global env id), car c using the same draw index as car c of tfx_set_poisson's stream.
- * The per-tick car COUNTS are exactly the reference's; gym_traffic/devrng.py mirrors the road draws on the host. */
+ * The per-tick car COUNTS are exactly the reference's; gym_traffic/devrng.py mirrors the road draws on the host.
+ * Heterogeneous handles: every car is archetypes[0] (:174); the call unbinds the rows of an earlier tfx_set_poisson. */
 int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed);
 /* Heterogeneous cars only: the archetype row of every car the count buffer of tfx_set_spawns adds
  * (`archetypes[random.randint(archetypes.shape[0])]`, traffic_env.py:164): device uint8
  * [n_ticks or 1][E][n_entry][per_road], entry j of a road = its j-th car of the tick in creation order (cars
  * beyond per_road, and every car while no buffer is bound or under TFX_SPAWN_PERIODIC - the reference's `regular`
- * generator yields archetypes[0], :174 - get row 0). */
+ * generator yields archetypes[0], :174 - get row 0).  The buffer replaces the rows a tfx_set_poisson stream bound. */
 int tfx_set_spawn_archetypes(tfx_handle h, const uint8_t *dev, int32_t per_road, int32_t per_tick);
 
 /* TrafficEnv._step (traffic_env.py:224-248), n_ticks times: phase/elapsed update, spawns,
@@ -293,7 +307,14 @@ int tfx_debug_fail_after(tfx_handle h, int32_t n_launches);
  * empty ticks between cars; else `burst` cars every `every` ticks), drawing each car's entry road
  * with rand.choice over n_choices entry points.  counts int32 [n_ticks][n_streams][n_columns] receives
  * the cars per entry road (choice c -> column column_of_choice[c]), made int32 [n_ticks][n_streams]
- * (may be NULL) the cars created. */
+ * (may be NULL) the cars created.
+ *
+ * tfx_arrivals_replay_rows is the same replay for a table of n_archetypes rows (1..TFX_MAX_ARCH): every Poisson car
+ * draws randint(n_archetypes) where SpawnSchedule._poisson_tick does (after its gap, before its entry road; nothing is
+ * drawn for one row), the regular generator draws no row (archetypes[0], traffic_env.py:174).  rows uint8
+ * [n_ticks][n_streams][n_columns][S] receives the row of the j-th car of each column in the tick, in creation order,
+ * for j < S (the bytes past a column's cars are left as they were); with n_archetypes = 1 the counts, made and the
+ * streams' final states are those of tfx_arrivals_replay. */
 typedef struct tfx_arrival_stream {
   uint32_t mt[624];
   int32_t pos;
@@ -303,6 +324,10 @@ typedef struct tfx_arrival_stream {
 int tfx_arrivals_replay(tfx_arrival_stream *streams, int32_t n_streams, int32_t n_ticks, int32_t poisson,
                         double mean_gap, int32_t every, int32_t burst, int32_t n_choices,
                         const int32_t *column_of_choice, int32_t n_columns, int32_t *counts, int32_t *made);
+int tfx_arrivals_replay_rows(tfx_arrival_stream *streams, int32_t n_streams, int32_t n_ticks, int32_t poisson,
+                             double mean_gap, int32_t every, int32_t burst, int32_t n_choices,
+                             const int32_t *column_of_choice, int32_t n_columns, int32_t *counts, int32_t *made,
+                             int32_t n_archetypes, int32_t S, uint8_t *rows);
 
 #ifdef __cplusplus
 }

@@ -58,12 +58,11 @@ inline int32_t mt_randint(tfx_arrival_stream *s, int32_t n) {  // RandomState.ra
   }
 }
 
-}  // namespace
-
-extern "C" int tfx_arrivals_replay(tfx_arrival_stream *streams, int32_t n_streams, int32_t n_ticks,
-                                   int32_t poisson, double mean_gap, int32_t every, int32_t burst,
-                                   int32_t n_choices, const int32_t *column_of_choice, int32_t n_columns,
-                                   int32_t *counts, int32_t *made) {
+// n_arch < 1: no archetype draws and no rows (tfx_arrivals_replay); otherwise randint(n_arch) per Poisson car and the
+// rows written to rows[t][stream][column][j < S] (tfx_arrivals_replay_rows)
+int replay(tfx_arrival_stream *streams, int32_t n_streams, int32_t n_ticks, int32_t poisson, double mean_gap,
+           int32_t every, int32_t burst, int32_t n_choices, const int32_t *column_of_choice, int32_t n_columns,
+           int32_t *counts, int32_t *made, int32_t n_arch, int32_t S, uint8_t *rows) {
   if (!streams || !counts || !column_of_choice || n_streams < 0 || n_ticks < 0 || n_choices < 1 || n_columns < 1)
     return TFX_EINVAL;
   std::memset(counts, 0, (size_t)n_ticks * n_streams * n_columns * sizeof(int32_t));
@@ -89,7 +88,11 @@ extern "C" int tfx_arrivals_replay(tfx_arrival_stream *streams, int32_t n_stream
             break;
           }
           s->gap = -1;
-          ++row[column_of_choice[mt_randint(s, n_choices)]];  // rand.choice(entrypoints) (:281)
+          // archetypes[random.randint(n)] (:164; spawner.py SpawnSchedule._poisson_tick), then rand.choice(entrypoints)
+          const int32_t a = n_arch > 0 ? mt_randint(s, n_arch) : 0;
+          const int32_t col = column_of_choice[mt_randint(s, n_choices)];  // (:281)
+          if (rows && row[col] < S) rows[(((size_t)t * n_streams + k) * n_columns + col) * S + row[col]] = (uint8_t)a;
+          ++row[col];
           ++n;
         }
       } else {
@@ -98,7 +101,9 @@ extern "C" int tfx_arrivals_replay(tfx_arrival_stream *streams, int32_t n_stream
         ++s->tick;
         if (due)
           for (int32_t b = 0; b < burst; ++b) {
-            ++row[column_of_choice[mt_randint(s, n_choices)]];
+            const int32_t col = column_of_choice[mt_randint(s, n_choices)];
+            if (rows && row[col] < S) rows[(((size_t)t * n_streams + k) * n_columns + col) * S + row[col]] = 0;  // archetypes[0] (:174)
+            ++row[col];
             ++n;
           }
       }
@@ -115,4 +120,24 @@ extern "C" int tfx_arrivals_replay(tfx_arrival_stream *streams, int32_t n_stream
     for (auto &th : pool) th.join();
   }
   return TFX_OK;
+}
+
+}  // namespace
+
+extern "C" int tfx_arrivals_replay(tfx_arrival_stream *streams, int32_t n_streams, int32_t n_ticks,
+                                   int32_t poisson, double mean_gap, int32_t every, int32_t burst,
+                                   int32_t n_choices, const int32_t *column_of_choice, int32_t n_columns,
+                                   int32_t *counts, int32_t *made) {
+  return replay(streams, n_streams, n_ticks, poisson, mean_gap, every, burst, n_choices, column_of_choice, n_columns,
+                counts, made, 0, 0, nullptr);
+}
+
+extern "C" int tfx_arrivals_replay_rows(tfx_arrival_stream *streams, int32_t n_streams, int32_t n_ticks,
+                                        int32_t poisson, double mean_gap, int32_t every, int32_t burst,
+                                        int32_t n_choices, const int32_t *column_of_choice, int32_t n_columns,
+                                        int32_t *counts, int32_t *made, int32_t n_archetypes, int32_t S,
+                                        uint8_t *rows) {
+  if (n_archetypes < 1 || n_archetypes > TFX_MAX_ARCH || S < 1 || !rows) return TFX_EINVAL;
+  return replay(streams, n_streams, n_ticks, poisson, mean_gap, every, burst, n_choices, column_of_choice, n_columns,
+                counts, made, n_archetypes, S, rows);
 }

@@ -118,7 +118,11 @@ struct tfx_handle_s {
   int greedy_spacing = 3;
   int poisson_rows = 1;        // ticks of arrival counts the Poisson buffer holds (tfx_step generates a call's worth up front)
   PoissonDev ps{};
-  void *dev_ps = nullptr;      // counts | gap_left | draws | cdf
+  // heterogeneous cars: the Poisson stream's archetype rows (k_poisson<true>), in dev_ps after the cdf; rows == nullptr:
+  // no rows drawn (single archetype, the regular stream).  Bound as Dev::spawn_arch while d.spawn_arch == prow.rows
+  PoissonRows prow{};
+  int n_arch = 1;              // rows of the archetype table (tfx_config.n_archetypes, at least 1)
+  void *dev_ps = nullptr;      // counts | gap_left | draws | cdf [| seq | rows]
   int *dev_greedy = nullptr;   // [E][I] actions
 };
 

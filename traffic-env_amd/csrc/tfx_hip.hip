@@ -113,13 +113,17 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
     // a chunk's kernels count ticks from 0 (row t of the count buffer is the chunk's tick t); a per-tick ACTION buffer is
     // indexed by the tick of the whole call, so its base moves along with the chunks
     const int *const act0 = h->d.action;
+    // the stream's archetype rows (heterogeneous cars) follow its counts row for row
+    const bool rows = h->prow.rows && h->d.spawn_arch == h->prow.rows;
     for (int done = 0; done < n_ticks && rc == TFX_OK;) {
       const int chunk = n_ticks - done < h->poisson_rows ? n_ticks - done : h->poisson_rows;
       rc = launch_poisson(h, chunk, st);
       h->d.spawn_stride = (long)h->d.E * h->d.n_entry;
+      if (rows) h->d.spawn_arch_stride = (long)h->d.E * h->d.n_entry * h->prow.S;
       if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
       if (rc == TFX_OK) rc = step_chunk(h, chunk, st);
       h->d.spawn_stride = 0;
+      if (rows) h->d.spawn_arch_stride = 0;
       h->d.action = act0;
       done += chunk;
     }
@@ -210,6 +214,7 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   if (!h) return fail(TFX_ENOMEM, "out of host memory");
   h->cfg = *cfg;
   h->het = het;
+  h->n_arch = n_arch;
   if (!het && cfg->n_archetypes == 1) {  // one ordinary row given through the table: it IS the archetype
     h->cfg.car_v = arch_rows[0][0]; h->cfg.car_l = arch_rows[0][1]; h->cfg.car_a = arch_rows[0][2];
     h->cfg.car_delta = arch_rows[0][3]; h->cfg.car_v0 = arch_rows[0][4]; h->cfg.car_b = arch_rows[0][5];
@@ -527,11 +532,31 @@ int tfx_set_actions(tfx_handle h, int32_t mode, const int32_t *dev, int32_t peri
   return TFX_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// the Poisson stream's archetype rows stop feeding the move kernels (its counts no longer do either, or another row
+// source takes over); rows bound through tfx_set_spawn_archetypes stay
+void unbind_stream_rows(tfx_handle h) {
+  Dev &d = h->d;
+  if (d.spawn_arch && d.spawn_arch == h->prow.rows) {
+    d.spawn_arch = nullptr;
+    d.spawn_arch_S = 0;
+    d.spawn_arch_stride = 0;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
 int tfx_set_spawns(tfx_handle h, int32_t mode, const int32_t *dev, int32_t period, int32_t per_tick) {
   if (int rc = check_handle(h, false)) return rc;
   Dev &d = h->d;
   ++h->input_gen;
   h->poisson = false;
+  unbind_stream_rows(h);
   if (mode == TFX_SPAWN_PERIODIC) {
     if (period < 1) return fail(TFX_EINVAL, "spawn period must be >= 1");
     d.spawn_period = period;
@@ -565,18 +590,35 @@ int tfx_set_poisson(tfx_handle h, double cars_per_tick, uint64_t seed, const uin
   if (!cdf || n_cdf < 1 || n_cdf > 65536) return fail(TFX_EINVAL, "gap table missing or too long");
   Dev &d = h->d;
   if (d.n_entry < 1) return fail(TFX_EINVAL, "no entry roads");
-  if (h->het) return fail(TFX_EINVAL, "the on-device Poisson stream draws no archetype rows: feed heterogeneous cars through "
-                                      "tfx_set_spawns + tfx_set_spawn_archetypes");
   ++h->input_gen;
+  unbind_stream_rows(h);
+  h->prow = PoissonRows{};
   if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
   // rows of E x n_entry counts: tfx_step generates that many ticks per launch (at most 64, at most ~32 MB)
   long rows = ((long)32 << 20) / ((long)d.E * d.n_entry * 4);
+  // heterogeneous cars: and E x n_entry x S archetype rows per tick within ~64 MB (cfg2: 17 MB per tick)
+  const int S = d.C - 2;
+  if (h->het) {
+    const long arows = ((long)64 << 20) / ((long)d.E * d.n_entry * S);
+    if (arows < rows) rows = arows;
+  }
   h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));
   const size_t n_counts = (size_t)h->poisson_rows * d.E * d.n_entry;
-  const size_t bytes = (n_counts + 2 * (size_t)d.E + (size_t)n_cdf) * 4;
+  const size_t n_seq = h->het ? (size_t)d.E * d.n_entry : 0;
+  const size_t bytes = (n_counts + 2 * (size_t)d.E + (size_t)n_cdf + n_seq) * 4 +
+                       (h->het ? (size_t)h->poisson_rows * d.E * d.n_entry * S : 0);
   HIPCHK(hipMalloc(&h->dev_ps, bytes));
-  HIPCHK(hipMemset(h->dev_ps, 0, bytes));
+  HIPCHK(hipMemset(h->dev_ps, 0, bytes));  // (seq starts at 0)
   int *base = (int *)h->dev_ps;
+  if (h->het) {
+    h->prow.seq = (unsigned *)(base + n_counts + 2 * (size_t)d.E + n_cdf);
+    h->prow.rows = (uint8_t *)(h->prow.seq + n_seq);
+    h->prow.S = S;
+    h->prow.n_arch = h->n_arch;
+    d.spawn_arch = h->prow.rows;
+    d.spawn_arch_S = S;
+    d.spawn_arch_stride = 0;  // (tfx_step's chunks: E x n_entry x S, next to spawn_stride)
+  }
   h->ps.counts = base;
   h->ps.gap_left = base + n_counts;
   h->ps.draws = (unsigned *)(base + n_counts + d.E);
@@ -601,6 +643,11 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed) {
   Dev &d = h->d;
   if (d.n_entry < 1) return fail(TFX_EINVAL, "no entry roads");
   ++h->input_gen;
+  // heterogeneous cars: every car of this stream is archetypes[0] (traffic_env.py:174) - no row buffer stays bound
+  d.spawn_arch = nullptr;
+  d.spawn_arch_S = 0;
+  d.spawn_arch_stride = 0;
+  h->prow = PoissonRows{};
   if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
   long rows = ((long)32 << 20) / ((long)d.E * d.n_entry * 4);
   h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));

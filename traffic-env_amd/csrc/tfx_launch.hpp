@@ -165,7 +165,12 @@ int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
   const Dev &d = h->d;
   const int threads = d.E <= 64 ? 1024 : (d.E <= 1024 ? 256 : 64);
   const int pg = d.E < h->n_cu * 16 ? d.E : h->n_cu * 16;
-  hipLaunchKernelGGL(k_poisson, dim3(pg), dim3(threads), ((size_t)d.n_entry + 2) * sizeof(int), st, d, h->ps, n_ticks);
+  if (h->prow.rows)  // (heterogeneous cars: the archetype row of every car too, and a running count per entry road)
+    hipLaunchKernelGGL(k_poisson<true>, dim3(pg), dim3(threads), ((size_t)2 * d.n_entry + 2) * sizeof(int), st, d, h->ps,
+                       n_ticks, h->prow);
+  else
+    hipLaunchKernelGGL(k_poisson<false>, dim3(pg), dim3(threads), ((size_t)d.n_entry + 2) * sizeof(int), st, d, h->ps,
+                       n_ticks, h->prow);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }

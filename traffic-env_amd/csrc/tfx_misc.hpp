@@ -189,9 +189,25 @@ struct PoissonDev {
 // n_ticks > 1: the counts of that many consecutive ticks, rows of E x n_entry each (tfx_step generates a whole
 // call's arrivals up front: they depend on nothing but the stream).  Inside an agent step (n_ticks = 1) an env
 // that stands still consumes nothing.
-__global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev ps, const int n_ticks) {
-  extern __shared__ int s_hist[];  // [n_entry] + 2 words
+//
+// ROWS (heterogeneous cars, the Poisson stream only): the archetype-table row of every car as well (add_new_cars draws
+// archetypes[randint(n)] per car, traffic_env.py:164) by rule 1 of include/tfx.h - car j (0-based) of the tick on entry
+// index ej of global env g takes row (u0 * n_arch) >> 32 of philox4x32({seq + j, g, TAG_ARCH, ej}, seed), seq = the
+// cars the stream has put on that entry road of the env before this tick (overflowed ones included).  Rows land at
+// rows[t][env][ej][j] for j < min(count, S), S = C - 2: no road takes more cars in one tick (add_car, :97-114), so
+// the move kernels never read a row past it.  The (entry, j) pairs of a tick are spread over the workgroup.
+struct PoissonRows {
+  uint8_t *rows;   // [n_ticks][E][n_entry][S]
+  unsigned *seq;   // [E][n_entry] cars put on each entry road so far
+  int S, n_arch;
+};
+constexpr unsigned TAG_ARCH = 0x41524348u;  // (TAG_GAP / TAG_ROAD: 0x47415021 / 0x524F4144, gym_traffic/devrng.py)
+
+template <bool ROWS>
+__global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev ps, const int n_ticks, const PoissonRows pr) {
+  extern __shared__ int s_hist[];  // [n_entry] + 2 words (ROWS: + [n_entry] running seq)
   int *s_first = s_hist + d.n_entry;  // lowest car index (relative) whose gap is non-zero | its gap
+  unsigned *s_seq = (unsigned *)(s_first + 2);
   const int tid = threadIdx.x, nthr = blockDim.x;
   for (int env = blockIdx.x; env < d.E; env += gridDim.x) {
     const bool frozen = n_ticks == 1 && env_frozen(d, env, *d.tickA);
@@ -199,6 +215,8 @@ __global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev 
     unsigned c0 = ps.draws[env];  // index of the next car
     const unsigned gid = (unsigned)(env + d.env_off);
     unsigned u[4];
+    if (ROWS)
+      for (int j = tid; j < d.n_entry; j += nthr) s_seq[j] = pr.seq[(size_t)env * d.n_entry + j];
     auto gap_of = [&](unsigned draw) {
       philox4x32(draw, gid, 0x47415021u, 0u, ps.seed_lo, ps.seed_hi, u);
       int k = 0;
@@ -207,6 +225,7 @@ __global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev 
     };
     __syncthreads();  // (every lane has read the env's state before lane 0 of an earlier iteration's store is overtaken)
     for (int t = 0; t < n_ticks; ++t) {
+      const unsigned c_tick = c0;  // (uniform over the workgroup, like c0)
       for (int j = tid; j < d.n_entry; j += nthr) s_hist[j] = 0;
       __syncthreads();
       if (!frozen && ps.regular) {
@@ -248,14 +267,36 @@ __global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev 
         }
       }
       __syncthreads();
+      if (ROWS && c0 != c_tick) {
+        // pair p = ej * S + j: lane tid starts at p = tid and steps by nthr (no division inside the loop)
+        const int S = pr.S;
+        const int dq = nthr / S, dr = nthr - dq * S;
+        int ej = tid / S, j = tid - ej * S;
+        uint8_t *rows = pr.rows + ((size_t)t * d.E + env) * d.n_entry * (size_t)S;
+        while (ej < d.n_entry) {
+          if (j < s_hist[ej]) {
+            philox4x32(s_seq[ej] + (unsigned)j, gid, TAG_ARCH, (unsigned)ej, ps.seed_lo, ps.seed_hi, u);
+            rows[(size_t)ej * S + j] = (uint8_t)(((unsigned long long)u[0] * (unsigned)pr.n_arch) >> 32);
+          }
+          j += dr;
+          ej += dq;
+          if (j >= S) { j -= S; ++ej; }
+        }
+        __syncthreads();  // (every lane has read s_seq before it moves)
+      }
       int *row = ps.counts + ((size_t)t * d.E + env) * d.n_entry;
-      for (int j = tid; j < d.n_entry; j += nthr) row[j] = s_hist[j];
+      for (int j = tid; j < d.n_entry; j += nthr) {
+        row[j] = s_hist[j];
+        if (ROWS) s_seq[j] += (unsigned)s_hist[j];
+      }
       __syncthreads();
     }
     if (tid == 0 && !frozen) {
       ps.gap_left[env] = gap;
       ps.draws[env] = c0;
     }
+    if (ROWS && !frozen)
+      for (int j = tid; j < d.n_entry; j += nthr) pr.seq[(size_t)env * d.n_entry + j] = s_seq[j];
   }
 }
 

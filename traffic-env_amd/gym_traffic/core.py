@@ -197,6 +197,7 @@ class TfxEngine(object):
         self._held_spawn = None
         self._action_bound = None
         self._spawn_bound = None
+        self._rows_key = None       # (pointer, S, per_tick) of the spawn-row buffer bound last (heterogeneous cars)
         self._stages = {}
         self.tick = 0
         # views with the reference's attribute names (traffic_env.py:372-376)
@@ -323,12 +324,14 @@ class TfxEngine(object):
 
     def set_poisson(self, cars_per_tick, seed=0):
         """On-device Poisson arrivals (the reference's generator, traffic_env.py:160-164, with a
-        counter-based RNG): cars_per_tick = cars_per_sec * rate for the whole env."""
+        counter-based RNG): cars_per_tick = cars_per_sec * rate for the whole env.  Heterogeneous cars: the
+        stream draws every car's archetype row too (rule 1 of include/tfx.h; devrng.PoissonMirror mirrors it)."""
         from gym_traffic.devrng import gap_table
         cdf = gap_table(cars_per_tick)
         nat.check(self.lib.tfx_set_poisson(self.h, float(cars_per_tick), int(seed),
                                            cdf.ctypes.data_as(C.c_void_p), int(cdf.size)))
         self._spawn_bound = None
+        self._rows_buf, self._rows_key = None, None
 
     def set_regular(self, cars_per_tick, seed=0):
         """On-device form of the reference's `regular` generator (traffic_env.py:167-176): ceil(cars_per_tick) cars
@@ -338,6 +341,7 @@ class TfxEngine(object):
         every, burst = round(1 / cars_per_tick), math.ceil(cars_per_tick)
         nat.check(self.lib.tfx_set_regular(self.h, int(every), int(burst), int(seed)))
         self._spawn_bound = None
+        self._rows_buf, self._rows_key = None, None   # (heterogeneous cars: every car is row 0, traffic_env.py:174)
 
     def set_greedy(self, spacing=3):
         """On-device greedy controller (algorithms/greedy.py:14-16), a decision every `spacing` ticks."""
@@ -383,12 +387,15 @@ class TfxEngine(object):
         if self.het and counts is not None:
             if rows is None:
                 nat.check(self.lib.tfx_set_spawn_archetypes(self.h, None, 0, 0))
-                self._rows_buf = None
+                self._rows_buf, self._rows_key = None, None
             else:
                 r8 = torch.as_tensor(np.ascontiguousarray(rows, np.uint8)).to(self.device) if not isinstance(rows, torch.Tensor) \
                     else rows.to(device=self.device, dtype=torch.uint8).contiguous()
                 self._rows_buf = r8
-                nat.check(self.lib.tfx_set_spawn_archetypes(self.h, _ptr(r8), int(r8.shape[-1]), 1 if per_tick else 0))
+                key = (r8.data_ptr(), int(r8.shape[-1]), bool(per_tick))
+                if self._rows_key != key:  # (an unchanged binding keeps the captured agent-step graph)
+                    nat.check(self.lib.tfx_set_spawn_archetypes(self.h, _ptr(r8), int(r8.shape[-1]), 1 if per_tick else 0))
+                    self._rows_key = key
         if period is not None:
             key = ("periodic", int(period))
             if self._spawn_bound != key:
@@ -418,7 +425,7 @@ class TfxEngine(object):
         car each entry road receives (tfx_set_spawn_archetypes); pairs with the count buffer already bound."""
         r8 = torch.as_tensor(np.ascontiguousarray(rows, np.uint8)).to(self.device) if not isinstance(rows, torch.Tensor) \
             else rows.to(device=self.device, dtype=torch.uint8).contiguous()
-        self._rows_buf = r8
+        self._rows_buf, self._rows_key = r8, None
         nat.check(self.lib.tfx_set_spawn_archetypes(self.h, _ptr(r8), int(r8.shape[-1]), 1 if per_tick else 0))
 
     def _as_dev_i32(self, a, key):

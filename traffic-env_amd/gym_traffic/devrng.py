@@ -6,6 +6,11 @@ distribution of `round(Exp(mean))` - the reference's gap rule (traffic_env.py:16
 round is half-to-even: gap k >= 1 covers [k - 1/2, k + 1/2], with the ties at even k).  Because both
 sides compare the same integers, `PoissonMirror` reproduces the device's (tick, road) sequence bit
 for bit; tests feed it to the oracle.
+
+With an archetype table of n > 1 rows the device also draws every car's row (rule 1 of include/tfx.h): car j (0-based)
+of a tick on entry index ej of global env g takes row (u0 * n) >> 32 of philox4x32({s + j, g, TAG_ARCH, ej}, seed),
+s = the cars the stream has put on that entry road of the env before the tick.  The mirrors keep s per (env, entry)
+and return the rows of each tick next to its counts.
 """
 import math
 
@@ -13,7 +18,7 @@ import numpy as np
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
-TAG_GAP, TAG_ROAD = 0x47415021, 0x524F4144
+TAG_GAP, TAG_ROAD, TAG_ARCH = 0x47415021, 0x524F4144, 0x41524348
 MASK = 0xFFFFFFFF
 
 
@@ -28,12 +33,12 @@ def philox4x32(c0, c1, c2, c3, k0, k1):
 
 
 def philox4x32_first(c0, c1, c2, c3, k0, k1):
-    """First output word of philox4x32 for an array of counters c0 (uint32 values in uint64 arrays)."""
-    import numpy as np
+    """First output word of philox4x32 for an array of counters c0 (uint32 values in uint64 arrays); c1..c3 are
+    scalars or arrays of c0's shape."""
     c0 = np.asarray(c0, np.uint64) & np.uint64(MASK)
-    c1 = np.full_like(c0, c1)
-    c2 = np.full_like(c0, c2)
-    c3 = np.full_like(c0, c3)
+    c1 = np.zeros_like(c0) + np.asarray(c1, np.uint64)
+    c2 = np.zeros_like(c0) + np.asarray(c2, np.uint64)
+    c3 = np.zeros_like(c0) + np.asarray(c3, np.uint64)
     m = np.uint64(MASK)
     s32 = np.uint64(32)
     for _ in range(10):
@@ -60,11 +65,62 @@ def gap_table(cars_per_tick, tail=1e-12):
     return np.asarray(cdf, np.uint32)
 
 
+class _Rows(object):
+    """Rule 1 for the envs of a mirror: `seq` [len(env_ids), n_entry] cars put on each entry road so far."""
+
+    def __init__(self, n_archetypes, per_road, n_envs, n_entry, k0, k1):
+        self.n_archetypes, self.S = int(n_archetypes), int(per_road)
+        if not 1 <= self.n_archetypes <= 64 or self.S < 1:
+            raise ValueError("n_archetypes must be in 1..64 and per_road >= 1")
+        self.seq = np.zeros((n_envs, n_entry), np.uint64)
+        self.k0, self.k1 = k0, k1
+
+    def tick(self, counts, env_ids, draw=True):
+        """uint8 [len(env_ids), n_entry, S]: row of car j of each entry road this tick for j < min(count, S), 0 past the
+        cars; advances seq by the full counts.  draw=False (the regular stream): every car is row 0."""
+        n_env, n_entry = counts.shape
+        rows = np.zeros((n_env, n_entry, self.S), np.uint8)
+        if draw and self.n_archetypes > 1:
+            for r, g in enumerate(env_ids):
+                m = np.minimum(counts[r], self.S).astype(np.int64)
+                if not m.any():
+                    continue
+                ej = np.repeat(np.arange(n_entry), m)
+                j = np.arange(ej.size) - np.repeat(np.cumsum(m) - m, m)
+                u = philox4x32_first((self.seq[r, ej] + j.astype(np.uint64)) & np.uint64(MASK), g, TAG_ARCH,
+                                     ej.astype(np.uint64), self.k0, self.k1)
+                rows[r, ej, j] = ((u * np.uint64(self.n_archetypes)) >> np.uint64(32)).astype(np.uint8)
+        self.seq += counts.astype(np.uint64)
+        return rows
+
+
+def _rows_or_none(n_archetypes, per_road, n_envs, n_entry, k0, k1):
+    if per_road is None:
+        if int(n_archetypes) > 1:
+            raise ValueError("rows of an archetype table need per_road (the engine's capacity - 2)")
+        return None
+    return _Rows(n_archetypes, per_road, n_envs, n_entry, k0, k1)
+
+
+def cars_of(counts, rows, entrypoints):
+    """One env's tick as the oracle takes it: (roads, rows) lists of its cars, grouped by entry road in entry-index order
+    and in creation order within a road (cars past the S rows held per road get row 0: they overflow)."""
+    roads, arch = [], []
+    S = rows.shape[-1]
+    for ej, c in enumerate(counts):
+        c = int(c)
+        roads += [int(entrypoints[ej])] * c
+        arch += [int(a) for a in rows[ej, :min(c, S)]] + [0] * max(0, c - S)
+    return roads, arch
+
+
 class PoissonMirror(object):
     """Draw 0 = the first gap; car c uses draw 1 + 2c for its entry road and draw 2 + 2c for the gap
     that follows it (the device evaluates 64 cars at a time from these fixed indices)."""
 
-    def __init__(self, cars_per_tick, seed, n_entry, env_ids):
+    def __init__(self, cars_per_tick, seed, n_entry, env_ids, n_archetypes=1, per_road=None):
+        """n_archetypes > 1 (with per_road = the engine's capacity - 2, the S of rule 1): next_tick also returns
+        the rows of the tick's cars (also with per_road given for a single row: all 0)."""
         self.cdf = [int(c) for c in gap_table(cars_per_tick)]
         self.cdf_np = np.asarray(self.cdf[:-1], np.uint64)
         self.k0, self.k1 = int(seed) & MASK, (int(seed) >> 32) & MASK
@@ -72,6 +128,7 @@ class PoissonMirror(object):
         self.env_ids = [int(e) for e in env_ids]
         self.gap = {e: -1 for e in self.env_ids}
         self.car = {e: 0 for e in self.env_ids}
+        self.rows = _rows_or_none(n_archetypes, per_road, len(self.env_ids), self.n_entry, self.k0, self.k1)
 
     def _gap(self, e, draw):
         u = philox4x32(draw & MASK, e, TAG_GAP, 0, self.k0, self.k1)[0]
@@ -81,7 +138,8 @@ class PoissonMirror(object):
         return k
 
     def next_tick(self, frozen=()):
-        """int32 [len(env_ids), n_entry] cars per entry road this tick (entry index order)."""
+        """int32 [len(env_ids), n_entry] cars per entry road this tick (entry index order); with rows: (counts, uint8
+        [len(env_ids), n_entry, S] row of car j of each road).  Envs in `frozen` (global ids) draw nothing."""
         out = np.zeros((len(self.env_ids), self.n_entry), np.int32)
         for row, e in enumerate(self.env_ids):
             if e in frozen:
@@ -105,7 +163,7 @@ class PoissonMirror(object):
                 if stop.size:
                     self.gap[e] = int(gaps[f]) - 1
                     break
-        return out
+        return out if self.rows is None else (out, self.rows.tick(out, self.env_ids))
 
 
 class RegularMirror(object):
@@ -114,16 +172,19 @@ class RegularMirror(object):
     round(1 / cars_per_tick); car c of env e (counted over the env's whole stream) enters on entry index
     floor(u * n_entry / 2^32) with u the first word of draw 1 + 2c of the env's Philox stream."""
 
-    def __init__(self, cars_per_tick, seed, n_entry, env_ids):
+    def __init__(self, cars_per_tick, seed, n_entry, env_ids, n_archetypes=1, per_road=None):
+        """n_archetypes / per_road as in PoissonMirror: the rows returned are all 0 (the reference's `regular`
+        generator yields archetypes[0], traffic_env.py:174)."""
         self.every, self.burst = round(1 / cars_per_tick), math.ceil(cars_per_tick)
         self.k0, self.k1 = int(seed) & MASK, (int(seed) >> 32) & MASK
         self.n_entry = int(n_entry)
         self.env_ids = [int(e) for e in env_ids]
         self.i = {e: 0 for e in self.env_ids}
         self.car = {e: 0 for e in self.env_ids}
+        self.rows = _rows_or_none(n_archetypes, per_road, len(self.env_ids), self.n_entry, self.k0, self.k1)
 
     def next_tick(self, frozen=()):
-        """int32 [len(env_ids), n_entry] cars per entry road this tick (entry index order)."""
+        """int32 [len(env_ids), n_entry] cars per entry road this tick (entry index order); with rows: (counts, rows)."""
         out = np.zeros((len(self.env_ids), self.n_entry), np.int32)
         for row, e in enumerate(self.env_ids):
             if e in frozen:
@@ -135,4 +196,4 @@ class RegularMirror(object):
                 ur = philox4x32_first(np.uint64(1) + np.uint64(2) * c, e, TAG_ROAD, 0, self.k0, self.k1)
                 np.add.at(out[row], ((ur * np.uint64(self.n_entry)) >> np.uint64(32)).astype(np.int64), 1)
                 self.car[e] += self.burst
-        return out
+        return out if self.rows is None else (out, self.rows.tick(out, self.env_ids, draw=False))

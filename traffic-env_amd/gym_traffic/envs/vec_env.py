@@ -9,6 +9,13 @@ reference env seeded `seed + env_id`), from the on-device form of the reference'
 use for throughput), from the on-device form of its `regular` generator (`spawn='regular_device'`: the reference's car
 counts per tick, entry roads from the same Philox streams) or from the on-device fixed-rate rule (`spawn='periodic'`).
 Sharding across GPUs is by env id (gym_traffic/distributed.py); envs share nothing.
+
+Mixed cars: `archetypes` takes the reference's `archetypes` table (traffic_env.py:35-43) as rows (v, l, a, delta, v0, b,
+T, s0) - the order of TfxEngine - and every car the envs make is a row of it, kept through every handoff (planes = 3,
+the transposed layout).  `poisson` replays the reference's `archetypes[random.randint(n)]` per car on each env's
+RandomState (env k equals a single-env TrafficEnv with the same table seeded `seed + k`); `device` draws the rows on the
+device by rule 1 of include/tfx.h (gym_traffic/devrng.py mirrors it); `regular`, `regular_device` and `periodic` make
+every car row 0, as the reference's `regular` generator does (traffic_env.py:174).
 """
 import numpy as np
 import torch
@@ -21,13 +28,18 @@ from gym_traffic.spawner import ArrivalStreams
 class TrafficVecEnv(object):
     def __init__(self, num_envs, m, n, length, capacity=20, rate=0.5, local_cars_per_sec=0.12,
                  spawn='poisson', spawn_period=8, entry_spec=0, learn_switch=False, validate=False,
-                 seed=0, env_id_offset=0, device=None):
+                 seed=0, env_id_offset=0, device=None, archetypes=None):
+        """archetypes: None (the reference's single archetype) or float [n, 8] rows (v, l, a, delta, v0, b, T, s0) of
+        the archetype table, n <= 64 - every spawn mode then makes mixed cars as the module docstring says."""
         self.num_envs = int(num_envs)
         self.graph = GridRoad(m, n, length)
         self.graph.generate_entrypoints(entry_spec)
+        tab = None if archetypes is None else np.asarray(archetypes, np.float32).reshape(-1, 8)
         self.engine = TfxEngine(m, n, length, capacity, n_envs=num_envs, rate=rate,
                                 learn_switch=learn_switch, validate=validate,
-                                entry_spec=entry_spec, device=device, env_id_offset=env_id_offset)
+                                entry_spec=entry_spec, device=device, env_id_offset=env_id_offset,
+                                archetypes=tab, **({} if tab is None else dict(planes=3, layout="transposed")))
+        self.archetypes = tab
         self.rate = float(rate)
         open_sides = 4 - bin(int(entry_spec) & 15).count('1')
         self.cars_per_sec = local_cars_per_sec * m * open_sides
@@ -38,9 +50,13 @@ class TrafficVecEnv(object):
             # env k of this shard is global env (env_id_offset + k): its stream does not depend on
             # how the envs are sharded over GPUs
             # (replayed in C for all envs at once: reference-identical arrivals at any batch size)
+            # (heterogeneous cars: the rows of every tick's cars too, S = capacity - 2 per road; bound next to the
+            # counts through a device buffer kept per tick count)
             self._arrivals = ArrivalStreams([seed + self.env_id_offset + k for k in range(self.num_envs)],
                                             spawn == 'poisson', self.graph.entrypoints, eng.entry_index,
-                                            max(1, eng.n_entry), self.cars_per_sec * self.rate)
+                                            max(1, eng.n_entry), self.cars_per_sec * self.rate,
+                                            **(dict(n_archetypes=len(tab), per_road=eng.C - 2) if eng.het else {}))
+            self._rows_dev = {}
         elif spawn == 'device':
             eng.set_poisson(self.cars_per_sec * self.rate, seed=seed)
         elif spawn == 'regular_device':
@@ -85,8 +101,7 @@ class TrafficVecEnv(object):
         elif actions is not None:
             eng.set_actions(actions)
         if self.spawn in ('poisson', 'regular'):
-            counts, _ = self._arrivals.next_ticks(int(n_ticks))
-            eng.set_spawns(counts=counts, per_tick=True)
+            self._bind_arrivals(int(n_ticks))
         eng.step(int(n_ticks))
         return eng.obs, eng.rewards, eng.done
 
@@ -102,9 +117,22 @@ class TrafficVecEnv(object):
         elif actions is not None:
             eng.set_actions(actions)
         if self.spawn in ('poisson', 'regular'):
+            self._bind_arrivals(n)
+        return eng.agent_step(n, remi=remi)
+
+    def _bind_arrivals(self, n):
+        """The host streams' next n ticks as the engine's per-tick spawn counts (and, heterogeneous cars, rows)."""
+        eng = self.engine
+        if not eng.het:
             counts, _ = self._arrivals.next_ticks(n)
             eng.set_spawns(counts=counts, per_tick=True)
-        return eng.agent_step(n, remi=remi)
+            return
+        counts, _, rows = self._arrivals.next_ticks(n)
+        dev = self._rows_dev.get(n)
+        if dev is None:
+            dev = self._rows_dev[n] = torch.empty(rows.shape, dtype=torch.uint8, device=eng.device)
+        dev.copy_(torch.from_numpy(rows))
+        eng.set_spawns(counts=counts, per_tick=True, rows=dev)
 
     def remi_reward(self):
         return self.engine.remi_reward()

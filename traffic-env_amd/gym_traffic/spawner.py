@@ -90,9 +90,15 @@ class ArrivalStreams(object):
     env k draws exactly what `SpawnSchedule(np.random.RandomState(seeds[k]), ...)` would - the same
     MT19937 words, the same legacy exponential / randint / choice arithmetic - at tens of nanoseconds
     per draw instead of microseconds, so reference-identical arrivals stay affordable for thousands of
-    envs.  `next_ticks(n)` returns (counts int32 [n, E, n_columns], made int32 [n, E])."""
+    envs.  `next_ticks(n)` returns (counts int32 [n, E, n_columns], made int32 [n, E]).
 
-    def __init__(self, seeds, poisson, entrypoints, column_of_road, n_columns, cars_per_tick):
+    With n_archetypes > 1 (the rows of the reference's `archetypes` table) every Poisson car also draws
+    `randint(n_archetypes)` where SpawnSchedule does (tfx_arrivals_replay_rows), and `next_ticks(n)` returns
+    (counts, made, rows uint8 [n, E, n_columns, per_road]): the row of the j-th car of each column in each tick, j <
+    per_road (an engine's capacity - 2: no road takes more cars in one tick); the regular generator's rows are 0."""
+
+    def __init__(self, seeds, poisson, entrypoints, column_of_road, n_columns, cars_per_tick, n_archetypes=1,
+                 per_road=None):
         import ctypes as C
         from gym_traffic import _native as nat
         self._C, self._lib = C, nat.lib()
@@ -110,24 +116,34 @@ class ArrivalStreams(object):
         self.every, self.burst = round(1 / cars_per_tick), math.ceil(cars_per_tick)
         self.columns = np.ascontiguousarray([column_of_road[int(rd)] for rd in entrypoints], np.int32)
         self.n_columns = int(n_columns)
+        self.n_archetypes = int(n_archetypes)
+        self.per_road = None if per_road is None else int(per_road)
+        if self.n_archetypes > 1 and self.per_road is None:
+            raise ValueError("rows of an archetype table need per_road (the engine's capacity - 2)")
         self._bufs = {}
 
-    def next_ticks(self, n, counts=None, made=None):
+    def next_ticks(self, n, counts=None, made=None, rows=None):
         C = self._C
-        if counts is None or made is None:      # buffers are kept per n and overwritten by the next call
-            buf = self._bufs.get(n)
+        with_rows = self.per_road is not None
+        if counts is None or made is None or (with_rows and rows is None):   # buffers are kept per n and overwritten
+            buf = self._bufs.get(n)                                         # by the next call
             if buf is None:
-                buf = self._bufs[n] = (np.empty((n, self.E, self.n_columns), np.int32), np.empty((n, self.E), np.int32))
+                buf = self._bufs[n] = (np.empty((n, self.E, self.n_columns), np.int32), np.empty((n, self.E), np.int32),
+                                       np.zeros((n, self.E, self.n_columns, self.per_road), np.uint8) if with_rows else None)
             counts = buf[0] if counts is None else counts
             made = buf[1] if made is None else made
-        rc = self._lib.tfx_arrivals_replay(C.cast(self._streams, C.c_void_p), self.E, int(n), int(self.poisson),
-                                           float(self.mean_gap), int(self.every), int(self.burst),
-                                           int(self.columns.size), self.columns.ctypes.data_as(C.c_void_p),
-                                           self.n_columns, counts.ctypes.data_as(C.c_void_p),
-                                           made.ctypes.data_as(C.c_void_p))
+            rows = buf[2] if rows is None else rows
+        args = (C.cast(self._streams, C.c_void_p), self.E, int(n), int(self.poisson), float(self.mean_gap),
+                int(self.every), int(self.burst), int(self.columns.size), self.columns.ctypes.data_as(C.c_void_p),
+                self.n_columns, counts.ctypes.data_as(C.c_void_p), made.ctypes.data_as(C.c_void_p))
+        if with_rows:
+            rc = self._lib.tfx_arrivals_replay_rows(*(args + (self.n_archetypes, self.per_road,
+                                                              rows.ctypes.data_as(C.c_void_p))))
+        else:
+            rc = self._lib.tfx_arrivals_replay(*args)
         if rc != 0:
             raise RuntimeError("tfx_arrivals_replay failed (%d)" % rc)
-        return counts, made
+        return (counts, made, rows) if with_rows else (counts, made)
 
     def random_state(self, k):
         """The RandomState env k's stream has reached (a copy; for checks and hand-over)."""
