@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TFX_ABI_VERSION 12
+#define TFX_ABI_VERSION 13
 #define TFX_KP 2 /* popped cars carried per road per tick on the parallel path; more -> exact serial path */
 #define TFX_MAX_ARCH 64 /* rows of the archetype table (traffic_env.py:35-43 ships one); a power of two */
 
@@ -216,6 +216,49 @@ int tfx_advance_finished_cars(tfx_handle h, void *stream);
  * n_ticks rows (row t feeds tick t of the step; rows after an env's overflow are not consumed). */
 int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float *aobs, float *areward,
                    uint8_t *adone, void *stream);
+
+/* Episodes on the device (default off: tfx_agent_step then does what it always did, launch for launch).  Every
+ * algorithm of the reference runs episodes of FLAGS.episode_len decisions and resets (`for i in range(FLAGS.episode_len)`,
+ * algorithms/greedy.py:13, fixed.py:16, spacedgreedy.py:16; traffic_test.py:20: 600 s / 5 s = 120 decisions) and prints
+ * each episode's return (print_running_stats(episode_reward(...))).  With enabled != 0 tfx_agent_step does three more
+ * things inside the same submission (and the same captured graph):
+ *
+ *   1. begin of the decision - masked restart: every env whose previous decision ended its episode is reset exactly as
+ *      tfx_reset_envs would reset it, its phases drawn on the device.  Rule 2: the phase of intersection i in episode
+ *      number n (ep_index: 0 for the episode the caller's tfx_reset started, 1 for the first restart, ...) of global env
+ *      g = env + env_id_offset is
+ *          phase = u0 & 1,  u = philox4x32(ctr = {n, g, TAG_EPISODE, i}, key = seed)
+ *      with TAG_EPISODE = 0x45504953 (the arrival streams use 0x47415021, 0x524F4144 and 0x41524348); it depends on
+ *      nothing else, so not on how envs are sharded over handles.  gym_traffic/devrng.py episode_phases mirrors it.
+ *      This is "next-step auto-reset": the observation a decision returns for an env that ended is its terminal one; the
+ *      new episode starts with the next decision, under that decision's action - the state sequence of the loop
+ *      `tfx_agent_step(); tfx_reset_envs(phases, terminated | truncated)`.  Arrival streams run on across a restart, as
+ *      they do under tfx_reset_envs.  Validate mode: the trip log of an ended episode stays readable until the next
+ *      decision begins (the restart clears n_trips).
+ *   2. the ticks, untouched.
+ *   3. end of the decision - accounting, per env, in decision order (float32 adds, so exactly reproducible):
+ *        ep_return[env][:] += areward;  ep_len[env] += 1
+ *        terminated = adone (overflow since the decision began);
+ *        truncated[env] = !terminated && max_decisions > 0 && ep_len[env] == max_decisions
+ *        where terminated | truncated:  final_return[env][:] = ep_return, final_len[env] = ep_len, both accumulators
+ *        cleared, ep_index[env] += 1, and the env is marked for the restart of step 1.
+ *      final_return / final_len keep the last ended episode's values elsewhere.
+ *
+ * tfx_reset and tfx_reset_envs clear ep_return, ep_len and the restart mark of the envs they reset (they abandon an
+ * episode; ep_index does not move).  The buffers are the caller's (device pointers, all required when enabled; the
+ * caller zeroes them): ep_return / final_return float32 [E][I], ep_len / final_len / ep_index int32 [E], truncated
+ * uint8 [E].  tfx_set_episodes itself clears the restart marks.  enabled == 0: `b` may be NULL, max_decisions and seed
+ * are ignored.  TFX_EINVAL for a negative max_decisions or a missing buffer, TFX_ESTATE before tfx_bind_buffers.
+ * max_decisions == 0: no time limit (episodes end on overflow only). */
+typedef struct tfx_episode_buffers {
+  float *ep_return;
+  int32_t *ep_len;
+  float *final_return;
+  int32_t *final_len;
+  uint8_t *truncated;
+  int32_t *ep_index;
+} tfx_episode_buffers;
+int tfx_set_episodes(tfx_handle h, int32_t enabled, int32_t max_decisions, uint64_t seed, const tfx_episode_buffers *b);
 
 /* remi (traffic_env.py:64-78) via TrafficEnv.remi_reward (:384-387) */
 int tfx_remi(tfx_handle h, void *stream);

@@ -115,6 +115,19 @@ struct Dev {
   long spawn_arch_stride;
 };
 
+// Episodes on the device (tfx_set_episodes, include/tfx.h), a parameter block of its own: only the kernels that begin
+// and end a decision (and k_reset) see it, every other kernel's arguments are what they were.  The caller's
+// accumulators, and two bytes per env of the handle's own - mark: the env's last decision ended its episode (the next
+// decision restarts it), last: the decision under way is the last one the time limit allows (k_episode_begin writes
+// it, the decision's tail reads it: nothing in a tail reads a word another lane of the same launch writes).
+struct EpDev {
+  int on, max;
+  unsigned seed_lo, seed_hi;
+  float *ep_return, *final_return;
+  int *ep_len, *final_len, *ep_index;
+  uint8_t *trunc, *mark, *last;
+};
+
 // The vehicle-update counter is spread over VEH_SLOTS words, one cache line apart: every wavefront
 // adds its share once, and with one word a small launch (one tile per wave, all waves finishing
 // together) spent ~25 us serialising 1280 atomics on it (cfg1 x 1024: k_move_t 30 us -> 5 us + walk).

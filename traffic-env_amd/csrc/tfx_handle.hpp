@@ -124,6 +124,9 @@ struct tfx_handle_s {
   int n_arch = 1;              // rows of the archetype table (tfx_config.n_archetypes, at least 1)
   void *dev_ps = nullptr;      // counts | gap_left | draws | cdf [| seq | rows]
   int *dev_greedy = nullptr;   // [E][I] actions
+  // episodes on the device (tfx_set_episodes): the parameter block, and its copy on the device (k_res reads it through a pointer)
+  EpDev ep{};
+  EpDev *dev_ep = nullptr;
 };
 
 namespace {

@@ -24,12 +24,14 @@ namespace {
 void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const void *aobs, const void *areward,
                const void *adone) {
   const Dev &d = h->d;
-  snprintf(key, n, "%llu|%u|%u|%d.%d.%d.%d|%d%d%d|%ld|%d|%d|%p|%p|%p|%p|%d|%d|%ld|%p|%d|%d|%p|%p|%p|%p|%p|%p|%p|%p",
+  snprintf(key, n, "%llu|%u|%u|%d.%d.%d.%d|%d%d%d|%ld|%d|%d|%p|%p|%p|%p|%d|%d|%ld|%p|%d|%d|%p|%p|%p|%p|%p|%p|%p|%p|%d.%d.%u.%u|%p|%p|%p|%p|%p|%p",
            h->input_gen, h->ps.seed_lo, h->ps.seed_hi, h->ps.n_cdf, h->ps.regular, h->ps.every, h->ps.burst, (int)h->poisson,
            (int)h->greedy, h->greedy_spacing, d.spawn_stride, n_ticks, remi, aobs, areward, adone, (const void *)d.action,
            d.action_mode, d.action_period, d.action_stride, (const void *)d.spawn, d.spawn_mode, d.spawn_period, (void *)d.xv,
            (void *)d.w, (void *)d.obs, (void *)d.rewards, (void *)d.leading, (void *)d.lastcar, (void *)d.waiting,
-           (void *)d.done_tick);
+           (void *)d.done_tick, h->ep.on, h->ep.max, h->ep.seed_lo, h->ep.seed_hi, (void *)h->ep.ep_return,
+           (void *)h->ep.ep_len, (void *)h->ep.final_return, (void *)h->ep.final_len, (void *)h->ep.trunc,
+           (void *)h->ep.ep_index);
 }
 
 }  // namespace
@@ -63,7 +65,7 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
     return rc;
   }
   // one graph per distinct launch sequence: everything baked into kernel arguments is in the key
-  char key[640];
+  char key[896];
   graph_key(h, key, sizeof key, n_ticks, remi, aobs, areward, adone);
   if (!h->ag_exec || h->ag_key != key) {
     if (h->ag_exec) { (void)hipGraphExecDestroy(h->ag_exec); h->ag_exec = nullptr; }
@@ -134,7 +136,7 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
 
 // the same as a captured graph: captured once per distinct sequence (graph_key), replayed afterwards
 int step_graph(tfx_handle h, int n_ticks, hipStream_t st) {
-  char key[640];
+  char key[896];
   graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
   if (!h->st_exec || h->st_key != key) {
     if (h->st_exec) { (void)hipGraphExecDestroy(h->st_exec); h->st_exec = nullptr; }
@@ -313,6 +315,8 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   const size_t o_lead = off;  off = align_up(off + ER * sizeof(float), 256);
   const size_t o_taila = off; off = align_up(off + (het ? ER * sizeof(int) : 0), 256);
   const size_t o_hb = off;    off = align_up(off + (d.layout == 1 ? ER : 0), 256);
+  const size_t o_ep = off;    off = align_up(off + 2 * (size_t)d.E, 256);  // episodes: mark | last (tfx_set_episodes)
+  const size_t o_epd = off;   off = align_up(off + sizeof(EpDev), 256);    // ... and the device copy of the block
   const size_t o_misc = off;  off = align_up(off + 128, 256);
   const size_t o_veh = off;   off = align_up(off + (size_t)VEH_SLOTS * VEH_STRIDE * sizeof(unsigned long long), 256);
   if (hipMalloc(&h->dev_scratch, off) != hipSuccess) {
@@ -343,6 +347,9 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   d.hb = d.layout == 1 ? (uint8_t *)(base + o_hb) : nullptr;
   d.het = het ? 1 : 0;
   d.taila = (int *)(base + o_taila);
+  h->ep.mark = (uint8_t *)(base + o_ep);
+  h->ep.last = h->ep.mark + d.E;
+  h->dev_ep = (EpDev *)(base + o_epd);
   if (het) {
     float tab[TFX_MAX_ARCH][ARCH_W] = {};
     for (int a = 0; a < n_arch; ++a) {
@@ -472,7 +479,7 @@ int tfx_reset(tfx_handle h, const int32_t *phase_init, void *stream) {
   HIPCHK(hipMemsetAsync(h->d.tickA, 0, sizeof(int), st));
   HIPCHK(hipMemsetAsync(h->d.tickB, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_reset, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0, st, h->d, phase_init,
-                     (const uint8_t *)nullptr);
+                     (const uint8_t *)nullptr, h->ep);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
@@ -481,8 +488,35 @@ int tfx_reset_envs(tfx_handle h, const int32_t *phase_init, const uint8_t *mask,
   if (int rc = check_handle(h, true)) return rc;
   if (!phase_init || !mask) return fail(TFX_EINVAL, "phase_init and mask are required");
   hipLaunchKernelGGL(k_reset, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0, (hipStream_t)stream,
-                     h->d, phase_init, mask);
+                     h->d, phase_init, mask, h->ep);
   HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_set_episodes(tfx_handle h, int32_t enabled, int32_t max_decisions, uint64_t seed, const tfx_episode_buffers *b) {
+  if (enabled) {  // (arguments first: they are checked even where no handle can exist)
+    if (max_decisions < 0) return fail(TFX_EINVAL, "max_decisions must be >= 0 (0: no time limit)");
+    if (!b) return fail(TFX_EINVAL, "null episode buffers");
+    if (!b->ep_return || !b->ep_len || !b->final_return || !b->final_len || !b->truncated || !b->ep_index)
+      return fail(TFX_EINVAL, "ep_return, ep_len, final_return, final_len, truncated and ep_index are required");
+  }
+  if (int rc = check_handle(h, true)) return rc;
+  EpDev &ep = h->ep;
+  HIPCHK(hipDeviceSynchronize());  // (decisions under way still read the marks)
+  HIPCHK(hipMemset(ep.mark, 0, 2 * (size_t)h->d.E));
+  ++h->input_gen;
+  ep.on = enabled ? 1 : 0;
+  ep.max = enabled ? max_decisions : 0;
+  ep.seed_lo = enabled ? (unsigned)seed : 0u;
+  ep.seed_hi = enabled ? (unsigned)(seed >> 32) : 0u;
+  ep.ep_return = enabled ? b->ep_return : nullptr;
+  ep.ep_len = enabled ? b->ep_len : nullptr;
+  ep.final_return = enabled ? b->final_return : nullptr;
+  ep.final_len = enabled ? b->final_len : nullptr;
+  ep.trunc = enabled ? b->truncated : nullptr;
+  ep.ep_index = enabled ? b->ep_index : nullptr;
+  HIPCHK(hipMemcpy(h->dev_ep, &ep, sizeof ep, hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());
   return TFX_OK;
 }
 

@@ -224,6 +224,8 @@ bool res_try(tfx_handle h, int epb) {
   static size_t granted = 64 * 1024;  // per instantiation <LPR, W>, process-wide
   if (lds > granted) {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(static_cast<void (*)(const Dev, const ResArgs)>(k_res<LPR, W>)),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(static_cast<void (*)(const Dev, const ResArgs)>(k_res<LPR, W, true>)),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
       (void)hipGetLastError();
       return false;  // the runtime does not grant that much LDS
@@ -314,23 +316,31 @@ int launch_res(tfx_handle h, int n_ticks, hipStream_t st, int tail = 0, int remi
   a.n_ent = 2 * (h->cfg.m + h->cfg.n);
   a.n_int = d.r - a.n_ent;
   a.cols = h->res_epb * d.R + 32;
+  a.ep = (tail && h->ep.on) ? h->dev_ep : nullptr;
   const int grid = (d.E + h->res_epb - 1) / h->res_epb;
   a.own_clock = grid == 1 ? 1 : 0;
   h->step_kernel = "k_res";
   const dim3 g(grid), b(h->res_threads);
+  // (the form with the episode accounting in its tail only while episodes are on)
+#define RES_GO(LPR_, W_)                                                                        \
+  do {                                                                                          \
+    if (a.ep) hipLaunchKernelGGL((k_res<LPR_, W_, true>), g, b, h->res_lds, st, d, a);          \
+    else hipLaunchKernelGGL((k_res<LPR_, W_>), g, b, h->res_lds, st, d, a);                      \
+  } while (0)
   if (h->res_lpr == 4) {
-    if (d.w) hipLaunchKernelGGL((k_res<4, true>), g, b, h->res_lds, st, d, a);
-    else hipLaunchKernelGGL((k_res<4, false>), g, b, h->res_lds, st, d, a);
+    if (d.w) RES_GO(4, true);
+    else RES_GO(4, false);
   } else if (h->res_lpr == 3) {
-    if (d.w) hipLaunchKernelGGL((k_res<3, true>), g, b, h->res_lds, st, d, a);
-    else hipLaunchKernelGGL((k_res<3, false>), g, b, h->res_lds, st, d, a);
+    if (d.w) RES_GO(3, true);
+    else RES_GO(3, false);
   } else if (h->res_lpr == 2) {
-    if (d.w) hipLaunchKernelGGL((k_res<2, true>), g, b, h->res_lds, st, d, a);
-    else hipLaunchKernelGGL((k_res<2, false>), g, b, h->res_lds, st, d, a);
+    if (d.w) RES_GO(2, true);
+    else RES_GO(2, false);
   } else {
-    if (d.w) hipLaunchKernelGGL((k_res<1, true>), g, b, h->res_lds, st, d, a);
-    else hipLaunchKernelGGL((k_res<1, false>), g, b, h->res_lds, st, d, a);
+    if (d.w) RES_GO(1, true);
+    else RES_GO(1, false);
   }
+#undef RES_GO
   HIPCHK(hipGetLastError());
   if (!a.own_clock) {  // every workgroup reads the clock at its start: it moves in a launch of its own
     hipLaunchKernelGGL(k_tick_add, dim3(1), dim3(1), 0, st, d, n_ticks);

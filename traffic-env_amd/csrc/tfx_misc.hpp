@@ -5,40 +5,52 @@
 
 namespace tfx {
 
-// traffic_env.py:259-272
-// mask == nullptr: every env; otherwise only the envs whose mask byte is non-zero (tfx_reset_envs)
-__global__ void k_reset(const Dev d, const int *phase_init, const uint8_t *mask) {
+// traffic_env.py:259-272 for road e of env `env` (id = env * R + e); `phase` is read for e < I only
+__device__ __forceinline__ void reset_road(const Dev &d, const int env, const int e, const long id, const int phase) {
+  if (d.layout == 0) {
+    d.xv[(size_t)id * d.C + 1] = make_float2(INFINITY, 0.0f);
+    if (d.w) d.w[(size_t)id * d.C + 1] = 0.0f;
+  } else {
+    d.leadx[id] = INFINITY;
+    d.hb[id] = 0;
+  }
+  d.leading[id] = 1;
+  d.lastcar[id] = 1;
+  d.tailx[id] = 0.0f;
+  d.rec[id] = make_int4(0, 0, 0, 0);
+  int *ob = d.obs + (size_t)env * d.obs_len;
+  if (e < d.r) {
+    ob[e] = 0;
+    d.waiting[(size_t)env * d.r + e] = 0;
+  }
+  if (e < d.I) {
+    ob[2 * d.r + e] = phase;
+    ob[2 * d.r + d.I + e] = 0;
+    d.passed_dst[(size_t)env * d.I + e] = 0;
+  }
+  if (e == 0) {
+    d.done_tick[env] = 0;
+    d.env_flag[env] = 0;
+    if (d.n_trips) d.n_trips[env] = 0;
+  }
+}
+
+// mask == nullptr: every env; otherwise only the envs whose mask byte is non-zero (tfx_reset_envs).
+// A reset from outside abandons the env's episode (tfx_set_episodes): accumulators and restart mark cleared.
+__global__ void k_reset(const Dev d, const int *phase_init, const uint8_t *mask, const EpDev ep) {
   const long total = (long)d.E * d.R;
   for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total;
        id += (long)gridDim.x * blockDim.x) {
     const int env = (int)(id / d.R);
     const int e = (int)(id - (long)env * d.R);
     if (mask && !mask[env]) continue;
-    if (d.layout == 0) {
-      d.xv[(size_t)id * d.C + 1] = make_float2(INFINITY, 0.0f);
-      if (d.w) d.w[(size_t)id * d.C + 1] = 0.0f;
-    } else {
-      d.leadx[id] = INFINITY;
-      d.hb[id] = 0;
-    }
-    d.leading[id] = 1;
-    d.lastcar[id] = 1;
-    d.tailx[id] = 0.0f;
-    d.rec[id] = make_int4(0, 0, 0, 0);
-    int *ob = d.obs + (size_t)env * d.obs_len;
-    if (e < d.r) {
-      ob[e] = 0;
-      d.waiting[(size_t)env * d.r + e] = 0;
-    }
-    if (e < d.I) {
-      ob[2 * d.r + e] = phase_init[(size_t)env * d.I + e];
-      ob[2 * d.r + d.I + e] = 0;
-      d.passed_dst[(size_t)env * d.I + e] = 0;
-    }
-    if (e == 0) {
-      d.done_tick[env] = 0;
-      d.env_flag[env] = 0;
-      if (d.n_trips) d.n_trips[env] = 0;
+    reset_road(d, env, e, id, e < d.I ? phase_init[(size_t)env * d.I + e] : 0);
+    if (ep.on) {
+      if (e < d.I) ep.ep_return[(size_t)env * d.I + e] = 0.0f;
+      if (e == 0) {
+        ep.ep_len[env] = 0;
+        ep.mark[env] = 0;
+      }
     }
   }
 }
@@ -202,6 +214,55 @@ struct PoissonRows {
   int S, n_arch;
 };
 constexpr unsigned TAG_ARCH = 0x41524348u;  // (TAG_GAP / TAG_ROAD: 0x47415021 / 0x524F4144, gym_traffic/devrng.py)
+constexpr unsigned TAG_EPISODE = 0x45504953u;  // rule 2 of include/tfx.h
+
+// Begin of a decision with episodes on (tfx_set_episodes), one launch ahead of the ticks: the envs whose last decision
+// ended their episode (mark, left by that decision's tail) restart as k_reset would restart them, the phase of
+// intersection i drawn by rule 2 of include/tfx.h - bit 0 of philox4x32({episode number, global env id, TAG_EPISODE,
+// i}, seed), the lane of road e < I drawing intersection e's.  Every env also learns whether the decision under way is
+// the last one its time limit allows (last).  The kernel reads mark and ep_len and writes neither.
+__global__ void k_episode_begin(const Dev d, const EpDev ep) {
+  const long total = (long)d.E * d.R;
+  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total;
+       id += (long)gridDim.x * blockDim.x) {
+    const int env = (int)(id / d.R);
+    const int e = (int)(id - (long)env * d.R);
+    if (e == 0) ep.last[env] = (ep.max > 0 && ep.ep_len[env] + 1 == ep.max) ? 1 : 0;
+    if (!ep.mark[env]) continue;
+    int phase = 0;
+    if (e < d.I) {
+      unsigned u[4];
+      philox4x32((unsigned)ep.ep_index[env], (unsigned)(env + d.env_off), TAG_EPISODE, (unsigned)e, ep.seed_lo,
+                 ep.seed_hi, u);
+      phase = (int)(u[0] & 1u);
+    }
+    reset_road(d, env, e, id, phase);
+  }
+}
+
+// End of a decision with episodes on, for intersection gi of env `env` / for the env itself (include/tfx.h, step 3);
+// `term`: the env overflowed since the decision began.  Called from the tails of both decision paths (k_agent_tail,
+// k_res) by the lane that already holds the reward / the done flag.
+__device__ __forceinline__ void episode_add_reward(const EpDev &ep, const int env, const size_t gi, const float rw, const bool term) {
+  float ret = ep.ep_return[gi] + rw;
+  if (term || ep.last[env]) {
+    ep.final_return[gi] = ret;
+    ret = 0.0f;
+  }
+  ep.ep_return[gi] = ret;
+}
+__device__ __forceinline__ void episode_end_env(const EpDev &ep, const int env, const bool term) {
+  const bool last = ep.last[env] != 0;
+  int len = ep.ep_len[env] + 1;
+  ep.trunc[env] = (!term && last) ? 1 : 0;
+  if (term || last) {
+    ep.final_len[env] = len;
+    len = 0;
+    ep.ep_index[env] += 1;
+  }
+  ep.ep_len[env] = len;
+  ep.mark[env] = (term || last) ? 1 : 0;
+}
 
 template <bool ROWS>
 __global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev ps, const int n_ticks, const PoissonRows pr) {
@@ -329,7 +390,8 @@ __global__ void k_clock_copy(const int *tickA, const int *tickB, int *clock2) {
 // k_remi) or the summed rewards as they stand, copied to areward; Repeater's observation (traffic_test.py:48-53): [sum
 // of passed | last detected | elapsed/100 * (2*phase - 1)] as float32, from the int obs the ticks left behind (passed
 // accumulated in place); the done flags: overflow in any tick since the decision began.  No element depends on another's.
-__global__ void k_agent_tail(const Dev d, const int remi, float *aobs, float *areward, uint8_t *adone, const int *first) {
+__global__ void k_agent_tail(const Dev d, const int remi, float *aobs, float *areward, uint8_t *adone, const int *first,
+                             const EpDev ep) {
   const int alen = 2 * d.r + d.I;
   const long n_int = (long)d.E * d.I, total = (long)d.E * alen;
   const int f = *first;
@@ -356,8 +418,13 @@ __global__ void k_agent_tail(const Dev d, const int remi, float *aobs, float *ar
         rw = d.rewards[g];
       }
       if (areward) areward[g] = rw;
+      if (ep.on) {
+        const int env = (int)(g / d.I);
+        episode_add_reward(ep, env, (size_t)g, rw, d.done_tick[env] > f);
+      }
     }
     if (adone && g < d.E) adone[g] = d.done_tick[g] > f ? 1 : 0;
+    if (ep.on && g < d.E) episode_end_env(ep, (int)g, d.done_tick[g] > f);
     if (aobs) {
       const int env = (int)(g / alen);
       const int k = (int)(g - (long)env * alen);

@@ -54,6 +54,8 @@ struct ResArgs {
   // LPR = 3 (two lanes per road, four on the roads without a predecessor): columns of the workgroup's LDS arrays, and
   // how many of an env's road slots are interior roads / roads without a predecessor (build_slots' order)
   int cols, n_int, n_ent;
+  // episodes (tfx_set_episodes): the handle's device copy of its EpDev while they are on, else null - read in the tail only
+  const EpDev *ep;
 };
 
 constexpr int RES_KH = 2;  // popped cars copied per handoff round
@@ -80,7 +82,9 @@ __host__ __device__ inline size_t res_lds_bytes(int Tr, int C, int epb, int I, i
 // Round 4 re-measured (make exp EXP=RW3:-DRES_WAVES=3 ...), cfg1 x 1024, a 10-tick call at 3 / 4 / 5 / 6 wavefronts per SIMD:
 // 100 / 103 / 117 / 133 us - and at 3 the bench's regions spread over 8.5 .. 13.7 us per tick (the misplaced launches)
 // against 8.5 .. 9.6 at 4; four lanes per road at 5 per SIMD (all four workgroups of a CU side by side): 150 us.
-template <int LPR, bool W>
+// EP: the form with the episode accounting of tfx_set_episodes in its tail (a.ep set); the plain form is the kernel it
+// always was
+template <int LPR, bool W, bool EP = false>
 #ifndef RES_WAVES
 #define RES_WAVES 4
 #endif
@@ -707,6 +711,7 @@ void k_res(const Dev d, const ResArgs a) {
       if (a.greedy_spacing > 0) a.greedy_act[(size_t)env * I + isec] = s_act[li];
     }
     if (a.tail && a.adone && e == 0) a.adone[env] = s_ovftick[env_l] > tick0 ? 1 : 0;
+    if (EP && a.tail && e == 0) episode_end_env(*a.ep, env, s_ovftick[env_l] > tick0);  // (tfx_set_episodes)
   }
   if (a.tail) {
     __syncthreads();  // the roads' waiting totals are in s_ovf
@@ -728,6 +733,7 @@ void k_res(const Dev d, const ResArgs a) {
         d.passed_dst[gi] = 0;
       }
       if (a.areward) a.areward[gi] = rw;
+      if (EP) episode_add_reward(*a.ep, env, gi, rw, s_ovftick[env_l] > tick0);
       if (a.aobs)  // elapsed / 100 * (2 * phase - 1), computed in binary64 like the reference's NumPy expression
         a.aobs[(size_t)env * (2 * d.r + I) + 2 * d.r + isec] = (float)((double)pl.y / 100.0 * (double)(2 * pl.x - 1));
     }

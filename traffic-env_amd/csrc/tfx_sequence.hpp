@@ -77,6 +77,13 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
   Dev &d = h->d;
   n_fused = n_pair = 0;
   SeqGuard guard(h);
+  if (h->ep.on) {
+    // episodes (tfx_set_episodes): the envs whose last decision ended their episode restart, ahead of the ticks and
+    // of any fork - the one launch the feature adds; the accounting rides in the decision's tail
+    TFX_INJECT(h);
+    hipLaunchKernelGGL(k_episode_begin, dim3(grid_for((long)d.E * d.R, h->n_cu)), dim3(256), 0, st, d, h->ep);
+    HIPCHK(hipGetLastError());
+  }
   if (res_usable(h, n_ticks)) {
     // every tick of the decision AND its tail (remi, observation, rewards, done flags) in one launch
     d.agent_mode = 1;
@@ -163,9 +170,9 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
   }
   d.agent_mode = guard.keep.agent_mode;  // the tail kernels below run outside the step's tick loop
   d.accum_rewards = guard.keep.accum_rewards;
-  if (remi || aobs || areward || adone) {
+  if (remi || aobs || areward || adone || h->ep.on) {
     hipLaunchKernelGGL(k_agent_tail, dim3(grid_for((long)d.E * (2 * d.r + d.I), h->n_cu)), dim3(256), 0, st, d, remi, aobs,
-                       areward, adone, d.agent_first);
+                       areward, adone, d.agent_first, h->ep);
     HIPCHK(hipGetLastError());
   }
   return TFX_OK;

@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("TFX_LIB", os.path.join(os.path.dirname(_HERE), "lib",
 MAX_ARCH = 64
 ACTION_BUFFER, ACTION_BROADCAST, ACTION_CYCLE, ACTION_GREEDY = 0, 1, 2, 3
 SPAWN_NONE, SPAWN_COUNTS, SPAWN_PERIODIC = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class TfxConfig(C.Structure):
@@ -32,6 +32,11 @@ class TfxBuffers(C.Structure):
                 ("trip_times", C.c_void_p), ("n_trips", C.c_void_p), ("trip_cap", C.c_int32)]
 
 
+class TfxEpisodeBuffers(C.Structure):
+    _fields_ = [("ep_return", C.c_void_p), ("ep_len", C.c_void_p), ("final_return", C.c_void_p),
+                ("final_len", C.c_void_p), ("truncated", C.c_void_p), ("ep_index", C.c_void_p)]
+
+
 class TfxError(RuntimeError):
     pass
 
@@ -49,6 +54,7 @@ _PROTOS = {
     "tfx_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfx_reset_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfx_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tfx_set_episodes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(TfxEpisodeBuffers)]),
     "tfx_set_actions": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "tfx_set_spawns": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "tfx_set_poisson": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_void_p, C.c_int32]),

@@ -200,6 +200,8 @@ class TfxEngine(object):
         self._rows_key = None       # (pointer, S, per_tick) of the spawn-row buffer bound last (heterogeneous cars)
         self._stages = {}
         self.tick = 0
+        # episodes on the device (set_episodes): None while off
+        self.ep_return = self.ep_len = self.final_return = self.final_len = self.truncated = self.ep_index = None
         # views with the reference's attribute names (traffic_env.py:372-376)
         self.passed = self.obs[:, :r]
         self.detected = self.obs[:, r:2 * r]
@@ -300,6 +302,44 @@ class TfxEngine(object):
         self._epoch += 1
         self._keep = (ph, m)
         self.done.masked_fill_(m.bool(), 0)
+
+    def set_episodes(self, max_decisions=None, seed=0, enabled=True):
+        """Episodes on the device (tfx_set_episodes, include/tfx.h): from now on every agent_step restarts the envs
+        whose last decision ended their episode (phases drawn on the device; devrng.episode_phases mirrors the draw),
+        runs the ticks, then accounts for the decision - all inside the decision's one submission.  max_decisions: the
+        time limit in decisions (None or 0: episodes end on overflow only).  Allocates (zeroed) and exposes
+            ep_return f32 [E,I], ep_len i32 [E]        the running episode
+            final_return f32 [E,I], final_len i32 [E]  the episode that ended last (valid where adone | truncated)
+            truncated u8 [E]                           the last decision hit the time limit (and did not overflow)
+            ep_index i32 [E]                           episodes ended so far = number of the running one
+        The observation agent_step returns for an env that ended is its terminal one; the env restarts at the
+        beginning of the NEXT decision, under that decision's action.  In validate mode the trip log of an ended
+        episode therefore stays readable until the next decision begins.  reset() / reset_envs() abandon the episode
+        of the envs they reset: accumulators cleared, ep_index unmoved.  enabled=False switches the feature off again
+        (the tensors are dropped)."""
+        E, I, dev = self.E, self.I, self.device
+        if not enabled:
+            with torch.cuda.device(dev):
+                nat.check(self.lib.tfx_set_episodes(self.h, 0, 0, 0, None))
+            self.ep_return = self.ep_len = self.final_return = self.final_len = self.truncated = self.ep_index = None
+            self._ep_keep = None
+            return
+        limit = 0 if max_decisions is None else int(max_decisions)
+        if limit < 0:
+            raise ValueError("max_decisions must be >= 0 (None / 0: no time limit)")
+        self.ep_return = torch.zeros((E, I), dtype=torch.float32, device=dev)
+        self.final_return = torch.zeros((E, I), dtype=torch.float32, device=dev)
+        self.ep_len = torch.zeros((E,), dtype=torch.int32, device=dev)
+        self.final_len = torch.zeros((E,), dtype=torch.int32, device=dev)
+        self.ep_index = torch.zeros((E,), dtype=torch.int32, device=dev)
+        self.truncated = torch.zeros((E,), dtype=torch.uint8, device=dev)
+        b = nat.TfxEpisodeBuffers()
+        b.ep_return, b.ep_len = _ptr(self.ep_return), _ptr(self.ep_len)
+        b.final_return, b.final_len = _ptr(self.final_return), _ptr(self.final_len)
+        b.truncated, b.ep_index = _ptr(self.truncated), _ptr(self.ep_index)
+        with torch.cuda.device(dev):
+            nat.check(self.lib.tfx_set_episodes(self.h, 1, limit, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(b)))
+        self._ep_keep = b
 
     def refresh(self, cars=None):
         """After writing xv / leading / lastcar from outside: push the ring-layout staging copy to

@@ -11,6 +11,9 @@ With an archetype table of n > 1 rows the device also draws every car's row (rul
 of a tick on entry index ej of global env g takes row (u0 * n) >> 32 of philox4x32({s + j, g, TAG_ARCH, ej}, seed),
 s = the cars the stream has put on that entry road of the env before the tick.  The mirrors keep s per (env, entry)
 and return the rows of each tick next to its counts.
+
+`episode_phases` mirrors the other draw the device makes: the light phases of an env that restarts on the device
+(tfx_set_episodes, rule 2 of include/tfx.h).
 """
 import math
 
@@ -19,6 +22,7 @@ import numpy as np
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 TAG_GAP, TAG_ROAD, TAG_ARCH = 0x47415021, 0x524F4144, 0x41524348
+TAG_EPISODE = 0x45504953
 MASK = 0xFFFFFFFF
 
 
@@ -48,6 +52,20 @@ def philox4x32_first(c0, c1, c2, c3, k0, k1):
         k0 = (k0 + W0) & MASK
         k1 = (k1 + W1) & MASK
     return c0
+
+
+def episode_phases(seed, env_ids, ep_index, I):
+    """int32 [len(env_ids), I]: the phases a restart on the device gives the intersections of global envs `env_ids`
+    at the start of their episode number `ep_index` (a scalar or one per env) - rule 2 of include/tfx.h: bit 0 of the
+    first word of philox4x32({episode number, global env id, TAG_EPISODE, intersection}, key = seed).  A pure function
+    of (seed, global env id, episode number, intersection)."""
+    env_ids = np.asarray(env_ids, np.uint64).reshape(-1)
+    n = np.zeros_like(env_ids) + (np.asarray(ep_index, np.int64).astype(np.uint64) & np.uint64(MASK))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    shape = (len(env_ids), int(I))
+    u0 = philox4x32_first(np.broadcast_to(n[:, None], shape), np.broadcast_to(env_ids[:, None], shape), TAG_EPISODE,
+                          np.broadcast_to(np.arange(int(I), dtype=np.uint64)[None, :], shape), seed & MASK, seed >> 32)
+    return (u0 & np.uint64(1)).astype(np.int32)
 
 
 def gap_table(cars_per_tick, tail=1e-12):

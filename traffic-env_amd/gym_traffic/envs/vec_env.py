@@ -16,6 +16,14 @@ the transposed layout).  `poisson` replays the reference's `archetypes[random.ra
 RandomState (env k equals a single-env TrafficEnv with the same table seeded `seed + k`); `device` draws the rows on the
 device by rule 1 of include/tfx.h (gym_traffic/devrng.py mirrors it); `regular`, `regular_device` and `periodic` make
 every car row 0, as the reference's `regular` generator does (traffic_env.py:174).
+
+Episodes: with `autoreset=True` the envs keep their episodes on the device (tfx_set_episodes, include/tfx.h).  Every
+`agent_step` first restarts the envs whose previous decision ended their episode - by overflow (`adone`) or by the time
+limit `episode_len` in decisions (`truncated`; the reference's algorithms run FLAGS.episode_len decisions per episode,
+algorithms/greedy.py:13) - with phases drawn on the device, and accounts for the decision at its end: `episode_return`,
+`episode_length` (running), `final_return`, `final_length` (of the episode that just ended; valid where
+`adone | truncated`).  The observation returned for an env that ended is its terminal one; its new episode starts with
+the next decision.  No host work per decision; `reset_done()` is not to be called in this mode.
 """
 import numpy as np
 import torch
@@ -28,9 +36,13 @@ from gym_traffic.spawner import ArrivalStreams
 class TrafficVecEnv(object):
     def __init__(self, num_envs, m, n, length, capacity=20, rate=0.5, local_cars_per_sec=0.12,
                  spawn='poisson', spawn_period=8, entry_spec=0, learn_switch=False, validate=False,
-                 seed=0, env_id_offset=0, device=None, archetypes=None):
+                 seed=0, env_id_offset=0, device=None, archetypes=None, autoreset=False, episode_len=None):
         """archetypes: None (the reference's single archetype) or float [n, 8] rows (v, l, a, delta, v0, b, T, s0) of
-        the archetype table, n <= 64 - every spawn mode then makes mixed cars as the module docstring says."""
+        the archetype table, n <= 64 - every spawn mode then makes mixed cars as the module docstring says.
+        autoreset / episode_len: episodes on the device, see the module docstring (episode_len needs autoreset; in
+        validate mode the trip log of an ended episode stays readable until the next decision begins)."""
+        if episode_len is not None and not autoreset:
+            raise ValueError("episode_len needs autoreset=True (the time limit is kept on the device)")
         self.num_envs = int(num_envs)
         self.graph = GridRoad(m, n, length)
         self.graph.generate_entrypoints(entry_spec)
@@ -69,6 +81,14 @@ class TrafficVecEnv(object):
             raise ValueError("spawn must be poisson|regular|device|regular_device|periodic|none")
         self._phase_rng = np.random.RandomState(seed + 7919 + self.env_id_offset)
         self.obs, self.rewards, self.done = eng.obs, eng.rewards, eng.done
+        self.autoreset = bool(autoreset)
+        self.episode_len = None if episode_len is None else int(episode_len)
+        if self.autoreset:
+            eng.set_episodes(max_decisions=self.episode_len, seed=seed)
+            self.truncated = eng.truncated
+            self.episode_return, self.episode_length = eng.ep_return, eng.ep_len
+            self.final_return, self.final_length = eng.final_return, eng.final_len
+            self.episode_index = eng.ep_index
 
     @property
     def observation_shape(self):
@@ -85,6 +105,9 @@ class TrafficVecEnv(object):
         """Start a new episode in the envs that are done (default: the `done` flags of the last step
         or decision), leaving the others running; returns the mask that was reset."""
         eng = self.engine
+        if self.autoreset:
+            raise RuntimeError("reset_done() with autoreset=True would reset the envs twice: the next agent_step "
+                               "restarts the envs that ended (adone | truncated) on the device")
         mask = eng.done.clone() if done is None else done      # (reset_envs clears eng.done of those envs)
         if phase_init is None:
             phase_init = self._phase_rng.randint(2, size=(eng.E, eng.I)).astype(np.int32)
