@@ -102,8 +102,9 @@ typedef struct tfx_config {
                             tfx_xv_pairs gives the size, tfx_export_ring / tfx_import_ring convert to
                             and from the ring layout.  Between calls a column may start one or two rows
                             down (the handle remembers where: two-tick passes, tfx_pair_ticks), so T is
-                            meaningful only together with its handle - snapshot, restore or edit the cars
-                            through tfx_export_ring / tfx_import_ring, never through T itself */
+                            meaningful only together with its handle - snapshot and restore envs with
+                            tfx_clone_envs, edit the cars through tfx_export_ring / tfx_import_ring, never
+                            through T itself */
   /* The reference's `archetypes` TABLE (traffic_env.py:35-43: float32 [n][10]; add_new_cars draws a row per car,
    * :164).  n_archetypes <= 1: the single archetype of the car_* fields above (the reference's default), and the
    * table is ignored.  n_archetypes in 2..TFX_MAX_ARCH, or one row whose delta is not 4: "heterogeneous cars" -
@@ -341,6 +342,60 @@ const char *tfx_step_kernel(tfx_handle h);
  * handle while it enqueues stays changed; the envs' state is then somewhere inside the failed call (reset or reload
  * it).  0 switches the injection off. */
 int tfx_debug_fail_after(tfx_handle h, int32_t n_launches);
+
+/* Clone env states on the device: env e of `dst` becomes a copy of env src_of_env[e] of `src`; -1 leaves env e
+ * untouched.  src_of_env is a DEVICE int32 [dst E] (a planner computes it with an argmax on the device).  One launch
+ * on `stream`, no host synchronisation, no bound pointer changes: captured agent-step / step graphs stay valid.  This is
+ * what lookahead controllers (K candidate light settings from the state an env is in), population methods with common
+ * random numbers, and snapshot / restore need; the reference has no counterpart (its env is one Python object,
+ * copy.deepcopy would do).
+ *
+ * dst != src (snapshot / branch: the second handle is the stash or the branch pool): both bound, on the same device,
+ *   with the same world - m, n, capacity, planes, layout, length, rate, validate, learn_switch, entry_spec, the same
+ *   archetype table, the same kinds ordering of storage slots, and the same per-tick constants (yellow_ticks, thresh,
+ *   detect_dist, overflow_penalty, eps); anything else is TFX_EINVAL with a message naming the field.  n_envs and
+ *   env_id_offset may differ.  An index outside [-1, src E) leaves env e untouched and is counted.  The launch is
+ *   ordered on `stream` only: work of `src` still pending on ANOTHER stream must be ordered before it by the caller
+ *   (an event, or a synchronisation).
+ * dst == src (in place, no staging buffer): a source must not itself be overwritten - env e is cloned only if
+ *   s = src_of_env[e] has src_of_env[s] == -1 or == s.  An env that breaks the rule, or whose index is outside
+ *   [-1, E), is LEFT UNTOUCHED and counted in a device counter that tfx_clone_skipped returns (and clears).  No index
+ *   array has undefined behaviour.  gym_traffic/devrng.py clone_plan states the rule in NumPy.
+ *
+ * What a clone always carries: the live cars (x, v; with planes == 3 the side word: spawn tick, and for heterogeneous
+ * cars the table row), leading, lastcar, the whole obs row, rewards, waiting, passed_dst, done_tick, in validate mode
+ * n_trips and the logged trip_times, the greedy controller's held decision, and every handle-owned word a later kernel
+ * reads for that env (the column offsets a two-tick pass leaves, tail and leader caches, road records, outboxes).
+ * After a clone ANY sequence of calls gives env e the bits it would give its source under the same inputs - also
+ * between two two-tick passes, without tfx_refresh.
+ *
+ * Clocks: every handle has its own device clock.  Across handles everything stored as a tick is rebased by
+ * tick(dst) - tick(src), read on the device: spawn ticks (the plain float, and modulo 2^24 inside the heterogeneous
+ * side word), non-zero done_tick stamps, and the handle's own per-env tick stamps (which env takes the serial advance
+ * or a pair of ticks one at a time - copied and rebased rather than cleared, so that a clone taken between
+ * tfx_move_cars and tfx_advance_finished_cars continues as its source does); trip times of a cloned env are then
+ * those of its source.  Input rules that read the clock (TFX_ACTION_CYCLE, TFX_SPAWN_PERIODIC) are inputs of the
+ * DESTINATION handle and are not cloned: a clone on a handle whose clock differs follows that handle's cycle.
+ *
+ * TFX_CLONE_STREAM: the clone also continues its source's on-device arrival stream (tfx_set_poisson / tfx_set_regular):
+ *   position (gap_left, draws, the per-entry car counters `seq` of rule 1) AND identity.  Every env has a stream id - a
+ *   handle-owned uint32, set to env + env_id_offset by tfx_set_poisson / tfx_set_regular - that keys its gap, road and
+ *   archetype-row draws (the `g` of rule 1); the flag copies id and position, so source and clone receive the same cars
+ *   on the same roads with the same rows from then on.  Needs the same stream in both handles (kind, seed, rate /
+ *   `every`, `burst`), else TFX_EINVAL.  Without the flag a clone keeps its own stream and position: same world,
+ *   independent arrivals.  Rule 2 (episode phases) stays keyed by the env's own global id.
+ * TFX_CLONE_EPISODE: with episodes on in both handles (tfx_set_episodes) ep_return, ep_len, ep_index and the restart mark
+ *   are copied too (final_* and truncated describe past decisions and are not).  Episodes off in both: the flag is
+ *   ignored; on in exactly one: TFX_EINVAL.  Without the flag the destination's accounting is left alone.
+ * tfx_debug_fail_after counts the clone's launch on `dst`. */
+enum { TFX_CLONE_STREAM = 1, TFX_CLONE_EPISODE = 2 };
+int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, int32_t flags, void *stream);
+/* envs tfx_clone_envs calls on `h` (as dst) left untouched against the caller's wish since the last call of this
+ * (synchronises the stream, clears the counter) */
+int tfx_clone_skipped(tfx_handle h, uint64_t *skipped, void *stream);   /* synchronises the stream */
+/* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
+ * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
+int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);
 
 /* Host-side replay of the reference's seeded arrival generators for many envs (no GPU involved): one
  * stream per env holds a legacy numpy RandomState's MT19937 state (`RandomState.get_state()[1:3]`)

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <new>
 
+#include "tfx_clone.hpp"
 #include "tfx_sequence.hpp"
 
 namespace {
@@ -234,7 +235,8 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   if (const char *gv = getenv("TFX_TT_SEGS")) h->tt_segs = atoi(gv);
   int dev = 0;
   hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+  if (hipGetDevice(&dev) == hipSuccess) h->device = dev;
+  if (hipGetDeviceProperties(&prop, dev) == hipSuccess)
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 
   Dev &d = h->d;
@@ -375,6 +377,7 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   d.risk_any = (int *)(base + o_misc + 56);   // two words
   d.slow_pairs = (unsigned long long *)(base + o_misc + 88);
   h->tick2 = (int *)(base + o_misc + 64);     // tickA, tickB, risk_any[2] of the second half
+  h->clone_skipped = (unsigned long long *)(base + o_misc + 96);
   // reciprocal division is used only if it is exact for this handle's constants on the whole
   // admitted numerator domain (2 x ~2^31 quotients, a few milliseconds; TFX_FASTDIV=0 disables)
   d.fastdiv = 0;
@@ -570,6 +573,14 @@ int tfx_set_actions(tfx_handle h, int32_t mode, const int32_t *dev, int32_t peri
 
 namespace {
 
+// every env's arrival stream starts out keyed by its global id (tfx_clone_envs with TFX_CLONE_STREAM copies ids)
+int init_stream_ids(tfx_handle h) {
+  std::vector<unsigned> ids((size_t)h->d.E);
+  for (int e = 0; e < h->d.E; ++e) ids[(size_t)e] = (unsigned)(e + h->d.env_off);
+  HIPCHK(hipMemcpy(h->ps_sid, ids.data(), ids.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+  return TFX_OK;
+}
+
 // the Poisson stream's archetype rows stop feeding the move kernels (its counts no longer do either, or another row
 // source takes over); rows bound through tfx_set_spawn_archetypes stay
 void unbind_stream_rows(tfx_handle h) {
@@ -639,13 +650,16 @@ int tfx_set_poisson(tfx_handle h, double cars_per_tick, uint64_t seed, const uin
   h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));
   const size_t n_counts = (size_t)h->poisson_rows * d.E * d.n_entry;
   const size_t n_seq = h->het ? (size_t)d.E * d.n_entry : 0;
-  const size_t bytes = (n_counts + 2 * (size_t)d.E + (size_t)n_cdf + n_seq) * 4 +
+  const size_t bytes = (n_counts + 3 * (size_t)d.E + (size_t)n_cdf + n_seq) * 4 +
                        (h->het ? (size_t)h->poisson_rows * d.E * d.n_entry * S : 0);
   HIPCHK(hipMalloc(&h->dev_ps, bytes));
   HIPCHK(hipMemset(h->dev_ps, 0, bytes));  // (seq starts at 0)
   int *base = (int *)h->dev_ps;
+  h->ps_sid = (unsigned *)(base + n_counts + 2 * (size_t)d.E + n_cdf);
+  if (int rc = init_stream_ids(h)) return rc;
+  h->ps_rate = cars_per_tick;
   if (h->het) {
-    h->prow.seq = (unsigned *)(base + n_counts + 2 * (size_t)d.E + n_cdf);
+    h->prow.seq = h->ps_sid + d.E;
     h->prow.rows = (uint8_t *)(h->prow.seq + n_seq);
     h->prow.S = S;
     h->prow.n_arch = h->n_arch;
@@ -657,6 +671,7 @@ int tfx_set_poisson(tfx_handle h, double cars_per_tick, uint64_t seed, const uin
   h->ps.gap_left = base + n_counts;
   h->ps.draws = (unsigned *)(base + n_counts + d.E);
   h->ps.cdf = (const unsigned *)(base + n_counts + 2 * (size_t)d.E);
+  h->ps.sid = h->ps_sid;
   h->ps.n_cdf = n_cdf;
   h->ps.regular = h->ps.every = h->ps.burst = 0;
   h->ps.seed_lo = (unsigned)seed;
@@ -686,11 +701,15 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed) {
   long rows = ((long)32 << 20) / ((long)d.E * d.n_entry * 4);
   h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));
   const size_t n_counts = (size_t)h->poisson_rows * d.E * d.n_entry;
-  const size_t bytes = (n_counts + 2 * (size_t)d.E) * 4;
+  const size_t bytes = (n_counts + 3 * (size_t)d.E) * 4;
   HIPCHK(hipMalloc(&h->dev_ps, bytes));
   HIPCHK(hipMemset(h->dev_ps, 0, bytes));  // (tick counters and car indices start at 0)
   int *base = (int *)h->dev_ps;
+  h->ps_sid = (unsigned *)(base + n_counts + 2 * (size_t)d.E);
+  if (int rc = init_stream_ids(h)) return rc;
+  h->ps_rate = 0.0;
   h->ps = PoissonDev{};
+  h->ps.sid = h->ps_sid;
   h->ps.counts = base;
   h->ps.gap_left = base + n_counts;
   h->ps.draws = (unsigned *)(base + n_counts + d.E);
@@ -920,6 +939,105 @@ int tfx_split_ticks(tfx_handle h, int64_t *ticks) {
 }
 
 const char *tfx_step_kernel(tfx_handle h) { return h ? h->step_kernel : ""; }
+
+int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, int32_t flags, void *stream) {
+  if (flags & ~(TFX_CLONE_STREAM | TFX_CLONE_EPISODE)) return fail(TFX_EINVAL, "unknown clone flags 0x%x", flags);
+  if (!src_of_env) return fail(TFX_EINVAL, "src_of_env is null");
+  if (int rc = check_handle(dst, true)) return rc;
+  if (int rc = check_handle(src, true)) return rc;
+  const tfx_config &a = dst->cfg, &b = src->cfg;
+  if (dst != src) {
+    if (dst->device != src->device)
+      return fail(TFX_EINVAL, "clone: the handles live on different devices (device %d / %d)", dst->device, src->device);
+#define TFX_SAME(field, fmt)                                                                                         \
+  if (a.field != b.field) return fail(TFX_EINVAL, "clone: the handles differ in " #field " (" fmt " / " fmt ")", a.field, b.field)
+    TFX_SAME(m, "%d"); TFX_SAME(n, "%d"); TFX_SAME(capacity, "%d"); TFX_SAME(planes, "%d"); TFX_SAME(layout, "%d");
+    TFX_SAME(length, "%g"); TFX_SAME(rate, "%g"); TFX_SAME(validate, "%d"); TFX_SAME(learn_switch, "%d");
+    TFX_SAME(entry_spec, "%u");
+    // (the constants every tick reads: a clone continues as its source does only under the same ones)
+    TFX_SAME(yellow_ticks, "%d"); TFX_SAME(thresh, "%g"); TFX_SAME(detect_dist, "%g"); TFX_SAME(overflow_penalty, "%g");
+    TFX_SAME(eps, "%g");
+#undef TFX_SAME
+    if (dst->het != src->het || dst->n_arch != src->n_arch)
+      return fail(TFX_EINVAL, "clone: the handles differ in n_archetypes (%d / %d rows)", dst->n_arch, src->n_arch);
+    const bool table = a.n_archetypes >= 1;
+    if (table != (b.n_archetypes >= 1) ||
+        (table ? memcmp(a.arch, b.arch, (size_t)dst->n_arch * sizeof a.arch[0]) != 0
+               : (a.car_v != b.car_v || a.car_l != b.car_l || a.car_a != b.car_a || a.car_delta != b.car_delta ||
+                  a.car_v0 != b.car_v0 || a.car_b != b.car_b || a.car_T != b.car_T || a.car_s0 != b.car_s0)))
+      return fail(TFX_EINVAL, "clone: the handles differ in the archetype table (arch)");
+    if (dst->h_slot_road != src->h_slot_road)
+      return fail(TFX_EINVAL, "clone: the handles differ in the kinds ordering of their storage slots (TFX_KINDS)");
+  }
+  CloneOpt o{};
+  o.same = dst == src ? 1 : 0;
+  o.skipped = dst->clone_skipped;
+  if (flags & TFX_CLONE_STREAM) {
+    if (!dst->poisson || !src->poisson)
+      return fail(TFX_EINVAL, "clone: TFX_CLONE_STREAM needs an on-device arrival stream (tfx_set_poisson / tfx_set_regular) "
+                              "in both handles");
+    const PoissonDev &p = dst->ps, &q = src->ps;
+    if (p.regular != q.regular) return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (poisson / regular)");
+    if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the stream seed");
+    if (p.regular ? (p.every != q.every) : (dst->ps_rate != src->ps_rate || p.n_cdf != q.n_cdf))
+      return fail(TFX_EINVAL, "clone: the handles differ in the stream rate");
+    if (p.burst != q.burst) return fail(TFX_EINVAL, "clone: the handles differ in the stream burst");
+    // (the same kind of stream on the same archetype table: both draw rows, or neither does)
+    o.stream = 1;
+    o.d_gap = p.gap_left; o.s_gap = q.gap_left;
+    o.d_draws = p.draws; o.s_draws = q.draws;
+    o.d_sid = dst->ps_sid; o.s_sid = src->ps_sid;
+    o.d_seq = dst->prow.seq; o.s_seq = src->prow.seq;
+  }
+  if (flags & TFX_CLONE_EPISODE) {
+    if (dst->ep.on != src->ep.on)
+      return fail(TFX_EINVAL, "clone: TFX_CLONE_EPISODE with episodes on in one handle only (tfx_set_episodes)");
+    if (dst->ep.on) {
+      o.episode = 1;
+      o.d_ep = dst->ep;
+      o.s_ep = src->ep;
+    }
+  }
+  if (dst->d.greedy_act && src->d.greedy_act) {
+    o.d_greedy = dst->d.greedy_act;
+    o.s_greedy = src->d.greedy_act;
+  }
+  TFX_INJECT(dst);
+  // a wavefront per (destination env, tile), four to a workgroup; a few workgroups per compute unit stride over more
+  const long items = (long)dst->d.E * dst->d.G;
+  long grid = (items + 3) / 4;
+  const long cap = (long)dst->n_cu * 16;
+  if (grid > cap) grid = cap;
+  hipLaunchKernelGGL(k_clone, dim3((unsigned)(grid < 1 ? 1 : grid)), dim3(256), 0, (hipStream_t)stream, dst->d, src->d,
+                     (const int *)src_of_env, o);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_clone_skipped(tfx_handle h, uint64_t *skipped, void *stream) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (!skipped) return fail(TFX_EINVAL, "skipped is null");
+  // read and cleared ON the stream, behind the clones enqueued there and ahead of the next one
+  unsigned long long v = 0;
+  HIPCHK(hipMemcpyAsync(&v, h->clone_skipped, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemsetAsync(h->clone_skipped, 0, sizeof v, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  *skipped = (uint64_t)v;
+  return TFX_OK;
+}
+
+int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream) {
+  if (int rc = check_handle(h, true)) return rc;
+  if (!out) return fail(TFX_EINVAL, "out is null");
+  const size_t n = (size_t)h->d.E * h->d.R;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  if (h->d.layout != 1) {
+    memset(out, 0, n);
+    return TFX_OK;
+  }
+  HIPCHK(hipMemcpy(out, h->d.hb, n, hipMemcpyDeviceToHost));
+  return TFX_OK;
+}
 
 int tfx_debug_fail_after(tfx_handle h, int32_t n_launches) {
   if (int rc = check_handle(h, false)) return rc;

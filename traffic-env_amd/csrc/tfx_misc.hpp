@@ -183,6 +183,9 @@ struct PoissonDev {
   int *counts;             // [E][n_entry]
   int *gap_left;           // [E] whole ticks until the next car; -1 = not drawn yet
   unsigned *draws;         // [E] index of the next car of the env's stream
+  // [E] stream id: what keys the env's gap, road and archetype-row draws.  The env's global id (env + env_id_offset)
+  // until tfx_clone_envs with TFX_CLONE_STREAM gives the env its source's - the clone then receives its source's cars
+  const unsigned *sid;
   const unsigned *cdf;     // [n_cdf] thresholds
   int n_cdf;
   unsigned seed_lo, seed_hi;
@@ -274,7 +277,7 @@ __global__ __launch_bounds__(1024) void k_poisson(const Dev d, const PoissonDev 
     const bool frozen = n_ticks == 1 && env_frozen(d, env, *d.tickA);
     int gap = ps.gap_left[env];
     unsigned c0 = ps.draws[env];  // index of the next car
-    const unsigned gid = (unsigned)(env + d.env_off);
+    const unsigned gid = ps.sid[env];  // (the global env id unless the env was cloned with its stream)
     unsigned u[4];
     if (ROWS)
       for (int j = tid; j < d.n_entry; j += nthr) s_seq[j] = pr.seq[(size_t)env * d.n_entry + j];

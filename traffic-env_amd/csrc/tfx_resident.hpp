@@ -265,7 +265,7 @@ void k_res(const Dev d, const ResArgs a) {
         if (envp < d.E && !(d.agent_mode && s_ovftick[el] > tick0)) {
           int gap = s_gap[el];
           unsigned c0 = s_draws[el];
-          const unsigned gid = (unsigned)(envp + d.env_off);
+          const unsigned gid = a.ps.sid[envp];
           unsigned u[4];
           auto gap_of = [&](unsigned draw) {
             philox4x32(draw, gid, 0x47415021u, 0u, a.ps.seed_lo, a.ps.seed_hi, u);

@@ -10,6 +10,7 @@ MAX_ARCH = 64
 ACTION_BUFFER, ACTION_BROADCAST, ACTION_CYCLE, ACTION_GREEDY = 0, 1, 2, 3
 SPAWN_NONE, SPAWN_COUNTS, SPAWN_PERIODIC = 0, 1, 2
 ABI_VERSION = 13
+CLONE_STREAM, CLONE_EPISODE = 1, 2      # flags of tfx_clone_envs
 
 
 class TfxConfig(C.Structure):
@@ -90,6 +91,9 @@ _PROTOS = {
     "tfx_split_ticks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "tfx_step_kernel": (C.c_char_p, [C.c_void_p]),
     "tfx_debug_fail_after": (C.c_int, [C.c_void_p, C.c_int32]),
+    "tfx_clone_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "tfx_clone_skipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "tfx_debug_head_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -341,6 +341,49 @@ class TfxEngine(object):
             nat.check(self.lib.tfx_set_episodes(self.h, 1, limit, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(b)))
         self._ep_keep = b
 
+    def clone_envs(self, src_of_env, source=None, streams=False, episodes=False):
+        """Env e becomes a copy of env src_of_env[e] of `source` (another engine of the same world; default: this
+        one), -1 leaves env e alone: tfx_clone_envs (include/tfx.h), one launch on the current stream, no host
+        synchronisation.  src_of_env: int [E], tensor (stays on the device) or array.  streams: the clone also
+        continues the source's on-device arrival stream (set_poisson / set_regular) - same cars on the same roads from
+        then on; episodes: the running episode's accounting travels too (set_episodes).  In place a source must not
+        itself be overwritten: envs that break the rule (or whose index is out of range) are left untouched and
+        counted, see clone_skipped() and devrng.clone_plan.  Returns the index tensor as bound."""
+        src = self if source is None else source
+        idx = src_of_env if isinstance(src_of_env, torch.Tensor) else torch.as_tensor(np.asarray(src_of_env, np.int32))
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        if idx.numel() != self.E:
+            raise ValueError("src_of_env must hold one index per env (%d), got %d" % (self.E, idx.numel()))
+        flags = (nat.CLONE_STREAM if streams else 0) | (nat.CLONE_EPISODE if episodes else 0)
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_clone_envs(self.h, src.h, _ptr(idx), flags, self._stream()))
+        self._epoch += 1
+        self._clone_keep = idx
+        # the Python-side done flags of the envs that were cloned: those of their sources
+        s = idx.long()
+        ok = (s >= 0) & (s < src.E)
+        sc = s.clamp(0, src.E - 1)
+        if src is self:
+            t = s[sc]
+            ok &= (t == -1) | (t == s)
+        self.done.copy_(torch.where(ok, src.done[sc], self.done))
+        return idx
+
+    def clone_skipped(self):
+        """Envs earlier clone_envs() calls left untouched against the caller's wish since the last call of this
+        (tfx_clone_skipped: returns and clears the device counter; synchronises the stream)."""
+        n = C.c_uint64()
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_clone_skipped(self.h, C.byref(n), self._stream()))
+        return int(n.value)
+
+    def head_rows(self):
+        """uint8 [E,R] (host): rows at the top of each road's column that hold no car (tfx_debug_head_rows; tests)."""
+        out = np.zeros((self.E, self.R), np.uint8)
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_debug_head_rows(self.h, out.ctypes.data_as(C.c_void_p), self._stream()))
+        return out
+
     def refresh(self, cars=None):
         """After writing xv / leading / lastcar from outside: push the ring-layout staging copy to
         the device layout (transposed handles) and rebuild the tail cache.

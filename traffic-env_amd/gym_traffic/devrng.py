@@ -68,6 +68,24 @@ def episode_phases(seed, env_ids, ep_index, I):
     return (u0 & np.uint64(1)).astype(np.int32)
 
 
+def clone_plan(src_of_env, n_src=None):
+    """The in-place rule of tfx_clone_envs (include/tfx.h) in NumPy: -> (applied bool [E], skipped int).  Env e takes
+    the state of env s = src_of_env[e] only if s is inside [0, E) and s is not itself overwritten by the call
+    (src_of_env[s] is -1 or s); -1 asks for nothing; every other env is left untouched and counted.  A self-reference
+    is applied (and changes nothing).  n_src: the env count of ANOTHER source handle - then only the range is checked,
+    a source cannot be overwritten."""
+    src = np.asarray(src_of_env, np.int64).reshape(-1)
+    E = len(src)
+    n = E if n_src is None else int(n_src)
+    inside = (src >= 0) & (src < n)
+    applied = inside.copy()
+    if n_src is None:
+        of_src = src[np.where(inside, src, 0)]
+        applied &= (of_src == -1) | (of_src == src)
+    skipped = int(np.count_nonzero((src != -1) & ~applied))
+    return applied, skipped
+
+
 def gap_table(cars_per_tick, tail=1e-12):
     """uint32 thresholds cdf[k] = floor(P(gap <= k) * 2^32), last entry 0xFFFFFFFF."""
     mean = 1.0 / float(cars_per_tick)

@@ -44,6 +44,11 @@ class TrafficVecEnv(object):
         if episode_len is not None and not autoreset:
             raise ValueError("episode_len needs autoreset=True (the time limit is kept on the device)")
         self.num_envs = int(num_envs)
+        # how this env was made (snapshot() makes another one like it)
+        self._ctor = dict(m=m, n=n, length=length, capacity=capacity, rate=rate, local_cars_per_sec=local_cars_per_sec,
+                          spawn=spawn, spawn_period=spawn_period, entry_spec=entry_spec, learn_switch=learn_switch,
+                          validate=validate, seed=seed, env_id_offset=env_id_offset, device=device,
+                          archetypes=archetypes, autoreset=autoreset, episode_len=episode_len)
         self.graph = GridRoad(m, n, length)
         self.graph.generate_entrypoints(entry_spec)
         tab = None if archetypes is None else np.asarray(archetypes, np.float32).reshape(-1, 8)
@@ -159,6 +164,41 @@ class TrafficVecEnv(object):
 
     def remi_reward(self):
         return self.engine.remi_reward()
+
+    # ---- branch, snapshot, restore (tfx_clone_envs, include/tfx.h) -------------------------------------------------
+    def clone_envs(self, src_of_env, source=None, streams=True, episodes=True):
+        """Env e becomes a copy of env src_of_env[e] of `source` (another TrafficVecEnv of the same world; default: this
+        one); -1 leaves env e alone.  One device launch, no host synchronisation (TfxEngine.clone_envs).  streams: the
+        clone also continues its source's arrival stream - on the device for spawn='device' | 'regular_device', and for
+        the host-replayed modes ('poisson' | 'regular') by copying the source envs' generator states, so env e replays
+        what its source would have replayed; both envs must use the same spawn mode.  episodes: with autoreset on in
+        both, the running episode's return / length / index travel too.  In place a source must not itself be
+        overwritten (devrng.clone_plan); such envs are left alone and counted in engine.clone_skipped()."""
+        other = self if source is None else source
+        eng = self.engine
+        on_device = self.spawn in ('device', 'regular_device')
+        if streams and self.spawn != other.spawn:
+            raise ValueError("clone_envs(streams=True) needs the same spawn mode in both envs (%r / %r)"
+                             % (self.spawn, other.spawn))
+        idx = eng.clone_envs(src_of_env, source=other.engine, streams=bool(streams and on_device),
+                             episodes=bool(episodes and self.autoreset and other.autoreset))
+        if streams and self.spawn in ('poisson', 'regular'):
+            from gym_traffic.devrng import clone_plan
+            host = idx.cpu().numpy()
+            applied, _ = clone_plan(host, None if other is self else other.num_envs)
+            self._arrivals.copy_streams(np.where(applied, host, -1), other._arrivals)
+        return idx
+
+    def snapshot(self):
+        """A new TrafficVecEnv of the same construction holding a clone of every env (streams and episodes included)."""
+        snap = TrafficVecEnv(self.num_envs, **self._ctor)
+        snap.reset(np.zeros((self.num_envs, self.engine.I), np.int32))
+        snap.clone_envs(torch.arange(self.num_envs, dtype=torch.int32), source=self)
+        return snap
+
+    def restore(self, snap):
+        """Every env back to the state `snap` (from snapshot()) holds."""
+        return self.clone_envs(torch.arange(self.num_envs, dtype=torch.int32), source=snap)
 
     # ---- validate-mode metrics, batched (reference: traffic_test.py:41-46, traffic_env.py:139-157, util.py:91-92) ----
     def light_times(self, actions):

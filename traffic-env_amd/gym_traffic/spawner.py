@@ -145,6 +145,21 @@ class ArrivalStreams(object):
             raise RuntimeError("tfx_arrivals_replay failed (%d)" % rc)
         return (counts, made, rows) if with_rows else (counts, made)
 
+    def copy_streams(self, src_of_env, source=None):
+        """Stream k becomes a copy of stream src_of_env[k] of `source` (default: this object) - MT19937 state, `gap`
+        and `tick` - for every k with src_of_env[k] >= 0; the sources are read before anything is written.  From
+        then on stream k replays what its source replays (TrafficVecEnv.clone_envs)."""
+        C = self._C
+        other = self if source is None else source
+        size = C.sizeof(self._streams[0])
+        todo = [(k, int(s)) for k, s in enumerate(np.asarray(src_of_env).reshape(-1)) if int(s) >= 0]
+        for _, s in todo:
+            if s >= other.E:
+                raise IndexError("stream %d of %d" % (s, other.E))
+        images = {s: C.string_at(C.addressof(other._streams[s]), size) for s in set(s for _, s in todo)}
+        for k, s in todo:
+            C.memmove(C.addressof(self._streams[k]), images[s], size)
+
     def random_state(self, k):
         """The RandomState env k's stream has reached (a copy; for checks and hand-over)."""
         rs = np.random.RandomState(0)
