@@ -393,6 +393,45 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
 /* envs tfx_clone_envs calls on `h` (as dst) left untouched against the caller's wish since the last call of this
  * (synchronises the stream, clears the counter) */
 int tfx_clone_skipped(tfx_handle h, uint64_t *skipped, void *stream);   /* synchronises the stream */
+/* Road measures on the device: the standard traffic measures of signal control - cars halted per approach, the queue at
+ * the stop line, speeds - as four words per road, from one read-only pass over the live cars (k_measure,
+ * csrc/tfx_measure.hpp).  The reference has no counterpart beyond cars_on_roads (traffic_env.py:214-218); without this
+ * call the route is tfx_export_ring of every ring slot and array code over the image.
+ *
+ * Definition, as a function of the image tfx_export_ring would produce at that moment (on a ring-layout handle: of xv
+ * itself) - so it is defined in every state a handle can be in: between two-tick passes, after a clone, after
+ * tfx_import_ring + tfx_refresh, between tfx_move_cars and tfx_advance_finished_cars.  For road e of env k take its cars
+ * in order from the head, j = 0 .. n-1: car j sits in ring slot wrap(leading + 1 + j) (wrap: a slot past C - 1 is slot
+ * 1, traffic_env.py:46-47), n is the count tfx_cars_on_roads returns; the fake leader is not a car.
+ *   in range    x >= x_from (x_from = -INFINITY: every car; a NaN x is out of range)
+ *   n_cars      the number of cars in range (x_from = -INFINITY: what tfx_cars_on_roads returns)
+ *   n_halted    the number of cars in range with v < halt_speed - float32, exact, strict
+ *   queue       the largest q such that cars 0 .. q-1 are all in range and all have v < halt_speed: the platoon
+ *               standing at the head of the road
+ *   speed_sum   the float32 sum of v over the cars in range: s = 0.0f, then s = s + v car by car in ascending j, one
+ *               rounding per add, never reassociated - the same bits on both layouts and from a host loop
+ * Outputs are device pointers, [E][R] by the reference's road id (like `leading`); any may be NULL, at least one must not
+ * be.  Without TFX_MEASURE_ACCUMULATE every bound output is overwritten (a road with no cars gets 0); with it
+ * out = out + value: integer adds, and ONE float32 add of the road's sum - a caller integrates over decisions (halted
+ * vehicle-ticks as a delay figure) by measuring between calls.
+ *
+ * One launch on `stream`, no host synchronisation; nothing in the handle or in the caller's bound state is written:
+ * captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the launch.  TFX_EINVAL: a NULL
+ * handle, a NULL `out`, all four pointers NULL, unknown flag bits, a NaN halt_speed or x_from (infinities are fine);
+ * TFX_ESTATE before tfx_bind_buffers.  gym_traffic/devrng.py road_measures states the definition in NumPy.
+ * TFX_MEASURE_GRID=n (read by tfx_create) caps the launch at n workgroups. */
+typedef struct tfx_measure_buffers {
+  int32_t *n_cars;     /* cars in range */
+  int32_t *n_halted;   /* cars in range with v < halt_speed */
+  int32_t *queue;      /* standing queue at the head of the road */
+  float *speed_sum;    /* sum of v over the cars in range */
+} tfx_measure_buffers;
+enum { TFX_MEASURE_ACCUMULATE = 1 };
+int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_measure_buffers *out, int32_t flags,
+                      void *stream);
+/* Test support: the launch geometry tfx_road_measures uses for this handle - workgroups, and wavefronts (one per
+ * (env, tile) item at a time; more items than wavefronts: every wavefront strides over several). */
+int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

@@ -133,6 +133,8 @@ struct tfx_handle_s {
   double ps_rate = 0.0;
   unsigned *ps_sid = nullptr;
   unsigned long long *clone_skipped = nullptr;
+  // tfx_road_measures (tfx_measure.hpp): TFX_MEASURE_GRID=n caps its launch at n workgroups (tests of its stride loop)
+  int measure_grid = 0;
 };
 
 namespace {

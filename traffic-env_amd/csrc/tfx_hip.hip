@@ -16,6 +16,7 @@
 #include <new>
 
 #include "tfx_clone.hpp"
+#include "tfx_measure.hpp"
 #include "tfx_sequence.hpp"
 
 namespace {
@@ -233,6 +234,7 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   if (const char *sv = getenv("TFX_SPLIT")) h->split = atoi(sv);
   if (const char *gv = getenv("TFX_TT_SEG")) h->tt_seg = atoi(gv);
   if (const char *gv = getenv("TFX_TT_SEGS")) h->tt_segs = atoi(gv);
+  if (const char *gv = getenv("TFX_MEASURE_GRID")) h->measure_grid = atoi(gv);
   int dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) == hipSuccess) h->device = dev;
@@ -757,6 +759,19 @@ int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
 
 }  // extern "C"
 
+namespace {
+
+// workgroups of a k_measure launch over E * G (env, tile) items (tfx_measure.hpp); cap > 0: TFX_MEASURE_GRID
+long measure_grid(int E, int G, int n_cu, int cap_env) {
+  const long items = (long)E * G;
+  long grid = (items + 3) / 4;
+  const long cap = cap_env > 0 ? (long)cap_env : (long)n_cu * 16;
+  if (grid > cap) grid = cap;
+  return grid < 1 ? 1 : grid;
+}
+
+}  // namespace
+
 extern "C" {
 
 int tfx_move_cars(tfx_handle h, void *stream) {
@@ -1023,6 +1038,37 @@ int tfx_clone_skipped(tfx_handle h, uint64_t *skipped, void *stream) {
   HIPCHK(hipMemsetAsync(h->clone_skipped, 0, sizeof v, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   *skipped = (uint64_t)v;
+  return TFX_OK;
+}
+
+int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_measure_buffers *out, int32_t flags,
+                      void *stream) {
+  if (!out) return fail(TFX_EINVAL, "out is null");
+  if (int rc = check_handle(h, false)) return rc;
+  if (!out->n_cars && !out->n_halted && !out->queue && !out->speed_sum)
+    return fail(TFX_EINVAL, "measures: every output pointer is null");
+  if (flags & ~TFX_MEASURE_ACCUMULATE) return fail(TFX_EINVAL, "unknown measure flags 0x%x", flags);
+  if (std::isnan(halt_speed) || std::isnan(x_from)) return fail(TFX_EINVAL, "measures: halt_speed / x_from is NaN");
+  if (int rc = check_handle(h, true)) return rc;
+  MeasureOut o{};
+  o.n_cars = out->n_cars;
+  o.n_halted = out->n_halted;
+  o.queue = out->queue;
+  o.speed_sum = out->speed_sum;
+  o.accumulate = (flags & TFX_MEASURE_ACCUMULATE) ? 1 : 0;
+  // a wavefront per (env, tile), four to a workgroup; a few workgroups per compute unit stride over more (as k_clone).
+  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
+  hipLaunchKernelGGL(k_measure, dim3((unsigned)measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid)), dim3(256), 0,
+                     (hipStream_t)stream, h->d, halt_speed, x_from, o);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  const long g = measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid);
+  if (grid) *grid = (int32_t)g;
+  if (waves) *waves = (int32_t)(g * 4);
   return TFX_OK;
 }
 

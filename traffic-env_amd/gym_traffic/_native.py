@@ -11,6 +11,7 @@ ACTION_BUFFER, ACTION_BROADCAST, ACTION_CYCLE, ACTION_GREEDY = 0, 1, 2, 3
 SPAWN_NONE, SPAWN_COUNTS, SPAWN_PERIODIC = 0, 1, 2
 ABI_VERSION = 13
 CLONE_STREAM, CLONE_EPISODE = 1, 2      # flags of tfx_clone_envs
+MEASURE_ACCUMULATE = 1                  # flag of tfx_road_measures
 
 
 class TfxConfig(C.Structure):
@@ -36,6 +37,10 @@ class TfxBuffers(C.Structure):
 class TfxEpisodeBuffers(C.Structure):
     _fields_ = [("ep_return", C.c_void_p), ("ep_len", C.c_void_p), ("final_return", C.c_void_p),
                 ("final_len", C.c_void_p), ("truncated", C.c_void_p), ("ep_index", C.c_void_p)]
+
+
+class TfxMeasureBuffers(C.Structure):
+    _fields_ = [("n_cars", C.c_void_p), ("n_halted", C.c_void_p), ("queue", C.c_void_p), ("speed_sum", C.c_void_p)]
 
 
 class TfxError(RuntimeError):
@@ -94,6 +99,8 @@ _PROTOS = {
     "tfx_clone_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "tfx_clone_skipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "tfx_debug_head_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfx_road_measures": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.POINTER(TfxMeasureBuffers), C.c_int32, C.c_void_p]),
+    "tfx_measure_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

@@ -13,6 +13,7 @@ State layout = the reference's arrays with a leading env dimension (traffic_env.
     leading/lastcar [E,R] i32   obs [E,2r+2I] i32   rewards [E,I] f32   waiting [E,r] i32
     passed_dst [E,I] u8   done_tick [E] i32
 """
+import collections
 import ctypes as C
 import os
 
@@ -26,6 +27,10 @@ ARCHETYPE = dict(car_v=11.11, car_l=4.0, car_a=3.0, car_delta=4.0, car_v0=13.89,
                  car_T=2.0, car_s0=1.0)
 # module constants of the reference (traffic_env.py:17-25)
 CONSTANTS = dict(yellow_ticks=6, thresh=0.2, detect_dist=10.0, overflow_penalty=10.0, eps=1e-8)
+
+
+# what road_measures() returns: four [E, R] device tensors by road id (tfx_road_measures, include/tfx.h)
+RoadMeasures = collections.namedtuple("RoadMeasures", "n_cars n_halted queue speed_sum")
 
 
 def _ptr(t):
@@ -183,6 +188,7 @@ class TfxEngine(object):
         self.passed_dst = torch.zeros((E, I), dtype=torch.uint8, device=dev)
         self.trip_times = torch.zeros((E, self.trip_cap), dtype=torch.float32, device=dev) if validate else None
         self._cars = torch.zeros((E, R), dtype=torch.int32, device=dev)
+        self._measures = None       # road_measures(): made on first use
         b = nat.TfxBuffers()
         b.xv = _ptr(self._t if self._t is not None else self._ring)
         b.w = _ptr(self._tw if self._tw is not None else self._ringw)
@@ -376,6 +382,41 @@ class TfxEngine(object):
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_clone_skipped(self.h, C.byref(n), self._stream()))
         return int(n.value)
+
+    def road_measures(self, halt_speed=0.1, x_from=None, accumulate=False, out=None):
+        """The standard traffic measures per road, from one read-only launch over the live cars (tfx_road_measures,
+        include/tfx.h; gym_traffic.devrng.road_measures states the definition in NumPy): -> RoadMeasures(n_cars,
+        n_halted, queue, speed_sum), [E, R] device tensors by road id (int32 x 3, float32).  A car is in range iff
+        x >= x_from (None: every car); halted iff in range and v < halt_speed; queue: the halted in-range platoon at
+        the head of the road; speed_sum: float32 sum of v over the cars in range, in car order.  accumulate: added to
+        the tensors instead of overwriting them (integrate over decisions by measuring between calls).  out: the
+        caller's RoadMeasures (any member None: not computed); default: tensors the engine allocates once, zeroed,
+        and reuses.  No host synchronisation; nothing of the env state is written."""
+        if out is None:
+            if self._measures is None:
+                i32 = [torch.zeros((self.E, self.R), dtype=torch.int32, device=self.device) for _ in range(3)]
+                self._measures = RoadMeasures(*i32, torch.zeros((self.E, self.R), dtype=torch.float32, device=self.device))
+            out = self._measures
+        else:
+            out = RoadMeasures(*out)
+            for name, t in zip(RoadMeasures._fields, out):
+                want = torch.float32 if name == "speed_sum" else torch.int32
+                if t is not None and (t.dtype != want or tuple(t.shape) != (self.E, self.R) or not t.is_contiguous()
+                                      or not t.is_cuda):
+                    raise ValueError("road_measures(out=): %s must be a contiguous %s [%d, %d] device tensor"
+                                     % (name, want, self.E, self.R))
+        b = nat.TfxMeasureBuffers()
+        b.n_cars, b.n_halted, b.queue, b.speed_sum = [_ptr(t) for t in out]
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_road_measures(self.h, float(halt_speed), float("-inf") if x_from is None else float(x_from),
+                                                 C.byref(b), nat.MEASURE_ACCUMULATE if accumulate else 0, self._stream()))
+        return out
+
+    def measure_launch(self):
+        """(workgroups, wavefronts) of the road_measures launch of this engine (tfx_measure_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_measure_launch(self.h, C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
 
     def head_rows(self):
         """uint8 [E,R] (host): rows at the top of each road's column that hold no car (tfx_debug_head_rows; tests)."""

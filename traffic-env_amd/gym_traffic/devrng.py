@@ -13,7 +13,8 @@ s = the cars the stream has put on that entry road of the env before the tick.  
 and return the rows of each tick next to its counts.
 
 `episode_phases` mirrors the other draw the device makes: the light phases of an env that restarts on the device
-(tfx_set_episodes, rule 2 of include/tfx.h).
+(tfx_set_episodes, rule 2 of include/tfx.h).  `clone_plan` and `road_measures` state two more device rules in NumPy: which
+envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per road.
 """
 import math
 
@@ -84,6 +85,47 @@ def clone_plan(src_of_env, n_src=None):
         applied &= (of_src == -1) | (of_src == src)
     skipped = int(np.count_nonzero((src != -1) & ~applied))
     return applied, skipped
+
+
+def road_measures(x, v, leading, lastcar, C, halt_speed=0.1, x_from=None):
+    """The definition of tfx_road_measures (include/tfx.h) in NumPy, over ring planes: x, v float32 [..., R, C] by ring
+    slot (what tfx_export_ring produces), leading / lastcar int [..., R].  -> (n_cars, n_halted, queue int32 [..., R],
+    speed_sum float32 [..., R]).  Car j of a road (j = 0: the head) sits in slot wrap(leading + 1 + j); it is in range
+    iff x >= x_from (None: -inf), halted iff in range and v < halt_speed (float32, strict); queue counts the cars from
+    the head on while every one is in range and halted; speed_sum adds v of the cars in range one at a time in
+    ascending j, in float32, starting from 0 - the order the device keeps, so the bits agree."""
+    C = int(C)
+    x = np.asarray(x, np.float32)
+    v = np.asarray(v, np.float32)
+    shape = x.shape[:-1]
+    x, v = x.reshape(-1, C), v.reshape(-1, C)
+    ld = np.asarray(leading, np.int64).reshape(-1)
+    lc = np.asarray(lastcar, np.int64).reshape(-1)
+    n = lc - ld + np.where(ld > lc, C - 1, 0)
+    halt = np.float32(halt_speed)
+    lo = np.float32(-np.inf if x_from is None else x_from)
+    rows = np.arange(len(ld))
+    cars = np.zeros(len(ld), np.int32)
+    halted = np.zeros(len(ld), np.int32)
+    queue = np.zeros(len(ld), np.int32)
+    unbroken = np.ones(len(ld), bool)
+    total = np.zeros(len(ld), np.float32)
+    for j in range(C - 1):
+        live = j < n
+        slot = ld + 1 + j
+        slot = np.where(slot > C - 1, slot - (C - 1), slot)
+        slot = np.where(live, slot, 0)
+        xj, vj = x[rows, slot], v[rows, slot]
+        with np.errstate(invalid="ignore"):
+            inr = live & (xj >= lo)
+            still = inr & (vj < halt)
+            added = (total + vj).astype(np.float32)        # one float32 add per car
+        cars += inr
+        halted += still
+        unbroken &= still | ~live
+        queue += unbroken & live
+        total = np.where(inr, added, total)
+    return cars.reshape(shape), halted.reshape(shape), queue.reshape(shape), total.reshape(shape)
 
 
 def gap_table(cars_per_tick, tail=1e-12):

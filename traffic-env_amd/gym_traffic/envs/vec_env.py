@@ -25,12 +25,18 @@ algorithms/greedy.py:13) - with phases drawn on the device, and accounts for the
 `adone | truncated`).  The observation returned for an env that ended is its terminal one; its new episode starts with
 the next decision.  No host work per decision; `reset_done()` is not to be called in this mode.
 """
+import collections
+
 import numpy as np
 import torch
 
 from gym_traffic.core import TfxEngine
 from gym_traffic.envs.roadgraph import GridRoad
 from gym_traffic.spawner import ArrivalStreams
+
+
+# what TrafficVecEnv.measures() returns: the engine's four per-road tensors and the views derived from them
+VecMeasures = collections.namedtuple("VecMeasures", "n_cars n_halted queue speed_sum halted cars mean_speed pressure")
 
 
 class TrafficVecEnv(object):
@@ -229,6 +235,37 @@ class TrafficVecEnv(object):
         if env is not None:
             return tt[env, :min(int(n[env]), eng.trip_cap)].copy()
         return [tt[k, :min(int(n[k]), eng.trip_cap)].copy() for k in range(eng.E)]
+
+    def measures(self, halt_speed=0.1, x_from=None, accumulate=False):
+        """The standard traffic measures of signal control for every env, on the device, with no host synchronisation:
+        one read-only launch over the live cars (TfxEngine.road_measures / tfx_road_measures, include/tfx.h) plus a few
+        torch expressions over its four words per road.  -> VecMeasures:
+            n_cars, n_halted, queue  int32 [E, R], speed_sum float32 [E, R] - per road id: cars with x >= x_from (None:
+                        all), those of them with v < halt_speed, the halted platoon at the head of the road, the sum of
+                        the speeds; the engine's tensors, overwritten by the next call - or, accumulate=True, added to
+                        (halted vehicle-decisions as a delay figure: measure once per decision)
+            halted, cars int64 [E] - sums of n_halted / n_cars over the train roads
+            mean_speed  float64 [E] - sum of speed_sum over the train roads / cars, 0 where there are no cars
+            pressure    int64 [E, I, 2] - max-pressure's quantity: for phase p the sum over the approach roads e of the
+                        intersection with graph.phases[e] == p of n_cars[e] - n_cars[graph.nexts[e]]
+        With accumulate=True the derived views are those of the accumulated tensors."""
+        eng = self.engine
+        rm = eng.road_measures(halt_speed=halt_speed, x_from=x_from, accumulate=accumulate)
+        r = eng.r
+        if getattr(self, "_pressure_idx", None) is None:
+            g = self.graph
+            self._pressure_idx = (torch.as_tensor(g.nexts[:r].astype(np.int64)).to(eng.device),
+                                  torch.as_tensor(g.dest[:r].astype(np.int64) * 2 + g.phases[:r]).to(eng.device))
+        nxt, cell = self._pressure_idx
+        n = rm.n_cars.long()
+        cars = n[:, :r].sum(dim=1)
+        halted = rm.n_halted[:, :r].sum(dim=1, dtype=torch.int64)
+        speed = rm.speed_sum[:, :r].sum(dim=1, dtype=torch.float64)
+        mean_speed = torch.where(cars > 0, speed / cars.clamp(min=1), torch.zeros_like(speed))
+        pressure = torch.zeros((eng.E, 2 * eng.I), dtype=torch.int64, device=eng.device)
+        pressure.index_add_(1, cell, n[:, :r] - n[:, nxt])
+        return VecMeasures(rm.n_cars, rm.n_halted, rm.queue, rm.speed_sum, halted, cars, mean_speed,
+                           pressure.view(eng.E, eng.I, 2))
 
     def cars_on_roads(self):
         return self.engine.cars_on_roads()
