@@ -432,6 +432,42 @@ int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_me
 /* Test support: the launch geometry tfx_road_measures uses for this handle - workgroups, and wavefronts (one per
  * (env, tile) item at a time; more items than wavefronts: every wavefront strides over several). */
 int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves);
+/* Road cells on the device: the discrete traffic state encoding - every road cut into n_cells cells along its length,
+ * each with its car count and the sum of its cars' speeds - from one read-only pass over the live cars (k_cells,
+ * csrc/tfx_cells.hpp).  tfx_road_measures generalised from four words per road to n_cells cells per road; without this
+ * call the route is tfx_export_ring of every ring slot and array code over the image.
+ *
+ * Definition, as a function of the image tfx_export_ring would produce at that moment (on a ring-layout handle: of xv
+ * itself), so it is defined in every state a handle can be in, as the measures are.  `edges` is a HOST array of
+ * n_cells + 1 float32 values, strictly ascending; -INFINITY is allowed as the first and +INFINITY as the last.  For road
+ * e of env k take its cars in order from the head, j = 0 .. n-1: car j sits in ring slot wrap(leading + 1 + j), n is the
+ * count tfx_cars_on_roads returns.
+ *   in range     edges[0] <= x < edges[n_cells]; a NaN x is in no cell
+ *   its cell     b = #{k in 1 .. n_cells-1 : x >= edges[k]} - comparisons only, no arithmetic on x, so there is nothing
+ *                for contraction or reciprocal forms to change; a car exactly on an edge belongs to the upper cell
+ *   n_cars[b]    the number of cars of cell b
+ *   speed_sum[b] s = 0.0f, then s = s + v over the cars of cell b in ascending j, one rounding per add, never
+ *                reassociated - the same bits on both layouts and from a host loop
+ * Outputs are device pointers, [E][R][n_cells] by the reference's road id; either may be NULL, not both.  Without
+ * TFX_CELLS_ACCUMULATE every bound output is overwritten (an empty cell gets 0); with it out = out + value: an integer add,
+ * and ONE float32 add per cell.  With n_cells = 1 and edges = {x_from, +INFINITY} the two planes are tfx_road_measures'
+ * n_cars and speed_sum, bit for bit.
+ *
+ * One launch on `stream`, no host synchronisation (the edges travel by value); nothing in the handle or in the caller's
+ * bound state is written: captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the
+ * launch.  TFX_MEASURE_GRID caps this launch too.  TFX_EINVAL: a NULL handle, NULL `edges`, NULL `out`, both pointers
+ * NULL, n_cells outside 1 .. TFX_MAX_CELLS, a NaN edge, edges not strictly ascending, unknown flag bits; TFX_ESTATE before
+ * tfx_bind_buffers.  gym_traffic/devrng.py road_cells states the definition in NumPy, cell_edges makes uniform edges. */
+#define TFX_MAX_CELLS 32
+typedef struct tfx_cell_buffers {
+  int32_t *n_cars;     /* [E][R][n_cells] by road id; may be NULL */
+  float *speed_sum;    /* [E][R][n_cells]; may be NULL */
+} tfx_cell_buffers;
+enum { TFX_CELLS_ACCUMULATE = 1 };
+int tfx_road_cells(tfx_handle h, const float *edges, int32_t n_cells, const tfx_cell_buffers *out, int32_t flags,
+                   void *stream);
+/* Test support: the launch geometry tfx_road_cells uses for this handle and n_cells - workgroups, and wavefronts. */
+int tfx_cells_launch(tfx_handle h, int32_t n_cells, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

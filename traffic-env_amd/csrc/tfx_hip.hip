@@ -15,6 +15,7 @@
 #include <cmath>
 #include <new>
 
+#include "tfx_cells.hpp"
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
 #include "tfx_sequence.hpp"
@@ -1066,6 +1067,53 @@ int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_me
 
 int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
+  const long g = measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid);
+  if (grid) *grid = (int32_t)g;
+  if (waves) *waves = (int32_t)(g * 4);
+  return TFX_OK;
+}
+
+int tfx_road_cells(tfx_handle h, const float *edges, int32_t n_cells, const tfx_cell_buffers *out, int32_t flags,
+                   void *stream) {
+  // (the arguments first, as tfx_road_measures does with `out`: each cause is named whatever state the handle is in)
+  if (!edges) return fail(TFX_EINVAL, "cells: edges is null");
+  if (!out) return fail(TFX_EINVAL, "cells: out is null");
+  if (!out->n_cars && !out->speed_sum) return fail(TFX_EINVAL, "cells: every output pointer is null");
+  if (n_cells < 1 || n_cells > TFX_MAX_CELLS)
+    return fail(TFX_EINVAL, "cells: n_cells %d is outside 1..%d", n_cells, TFX_MAX_CELLS);
+  if (flags & ~TFX_CELLS_ACCUMULATE) return fail(TFX_EINVAL, "unknown cell flags 0x%x", flags);
+  for (int k = 0; k <= n_cells; ++k)
+    if (std::isnan(edges[k])) return fail(TFX_EINVAL, "cells: edge %d is NaN", k);
+  for (int k = 0; k < n_cells; ++k)
+    if (!(edges[k] < edges[k + 1]))
+      return fail(TFX_EINVAL, "cells: edges are not strictly ascending at %d (%g, %g)", k, edges[k], edges[k + 1]);
+  if (int rc = check_handle(h, true)) return rc;
+  CellEdges ed;
+  ed.lo = edges[0];
+  ed.hi = edges[n_cells];
+  for (int k = 0; k < TFX_MAX_CELLS; ++k) ed.inner[k] = (k >= 1 && k < n_cells) ? edges[k] : INFINITY;
+  CellOut o{};
+  o.n_cars = out->n_cars;
+  o.speed_sum = out->speed_sum;
+  o.accumulate = (flags & TFX_CELLS_ACCUMULATE) ? 1 : 0;
+  // k_measure's launch (a wavefront per (env, tile), four to a workgroup, the same cap), instantiated on the cell bound.
+  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
+  const dim3 grid((unsigned)measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid));
+  const int B = n_cells;
+  if (B <= 8)
+    hipLaunchKernelGGL(k_cells<8>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
+  else if (B <= 16)
+    hipLaunchKernelGGL(k_cells<16>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
+  else
+    hipLaunchKernelGGL(k_cells<32>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_cells_launch(tfx_handle h, int32_t n_cells, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (n_cells < 1 || n_cells > TFX_MAX_CELLS)
+    return fail(TFX_EINVAL, "cells: n_cells %d is outside 1..%d", n_cells, TFX_MAX_CELLS);
   const long g = measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid);
   if (grid) *grid = (int32_t)g;
   if (waves) *waves = (int32_t)(g * 4);

@@ -12,6 +12,8 @@ SPAWN_NONE, SPAWN_COUNTS, SPAWN_PERIODIC = 0, 1, 2
 ABI_VERSION = 13
 CLONE_STREAM, CLONE_EPISODE = 1, 2      # flags of tfx_clone_envs
 MEASURE_ACCUMULATE = 1                  # flag of tfx_road_measures
+CELLS_ACCUMULATE = 1                    # flag of tfx_road_cells
+MAX_CELLS = 32                          # TFX_MAX_CELLS
 
 
 class TfxConfig(C.Structure):
@@ -41,6 +43,10 @@ class TfxEpisodeBuffers(C.Structure):
 
 class TfxMeasureBuffers(C.Structure):
     _fields_ = [("n_cars", C.c_void_p), ("n_halted", C.c_void_p), ("queue", C.c_void_p), ("speed_sum", C.c_void_p)]
+
+
+class TfxCellBuffers(C.Structure):
+    _fields_ = [("n_cars", C.c_void_p), ("speed_sum", C.c_void_p)]
 
 
 class TfxError(RuntimeError):
@@ -101,6 +107,8 @@ _PROTOS = {
     "tfx_debug_head_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfx_road_measures": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.POINTER(TfxMeasureBuffers), C.c_int32, C.c_void_p]),
     "tfx_measure_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_road_cells": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(TfxCellBuffers), C.c_int32, C.c_void_p]),
+    "tfx_cells_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

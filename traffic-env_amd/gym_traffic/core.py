@@ -31,6 +31,8 @@ CONSTANTS = dict(yellow_ticks=6, thresh=0.2, detect_dist=10.0, overflow_penalty=
 
 # what road_measures() returns: four [E, R] device tensors by road id (tfx_road_measures, include/tfx.h)
 RoadMeasures = collections.namedtuple("RoadMeasures", "n_cars n_halted queue speed_sum")
+# what road_cells() returns: two [E, R, B] device tensors by road id and cell (tfx_road_cells, include/tfx.h)
+RoadCells = collections.namedtuple("RoadCells", "n_cars speed_sum")
 
 
 def _ptr(t):
@@ -189,6 +191,7 @@ class TfxEngine(object):
         self.trip_times = torch.zeros((E, self.trip_cap), dtype=torch.float32, device=dev) if validate else None
         self._cars = torch.zeros((E, R), dtype=torch.int32, device=dev)
         self._measures = None       # road_measures(): made on first use
+        self._cells = {}            # road_cells(): made on first use, per number of cells
         b = nat.TfxBuffers()
         b.xv = _ptr(self._t if self._t is not None else self._ring)
         b.w = _ptr(self._tw if self._tw is not None else self._ringw)
@@ -416,6 +419,44 @@ class TfxEngine(object):
         """(workgroups, wavefronts) of the road_measures launch of this engine (tfx_measure_launch; tests)."""
         g, w = C.c_int32(), C.c_int32()
         nat.check(self.lib.tfx_measure_launch(self.h, C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def road_cells(self, edges, accumulate=False, out=None):
+        """Cars and speeds per cell of road, from one read-only launch over the live cars (tfx_road_cells, include/tfx.h;
+        gym_traffic.devrng.road_cells states the definition in NumPy): -> RoadCells(n_cars int32, speed_sum float32),
+        [E, R, B] device tensors by road id and cell.  edges: B + 1 strictly ascending float32 values (host; -inf / +inf
+        allowed at the ends, devrng.cell_edges makes uniform ones); a car is in cell b iff edges[b] <= x < edges[b + 1];
+        speed_sum: float32 sum of v over the cell's cars, in car order.  accumulate: added to the tensors instead of
+        overwriting them.  out: the caller's RoadCells (a member None: not computed); default: tensors the engine
+        allocates once per B, zeroed, and reuses.  No host synchronisation; nothing of the env state is written."""
+        e = np.ascontiguousarray(np.asarray(edges, np.float32).reshape(-1))
+        B = len(e) - 1
+        shape = (self.E, self.R, B)
+        if not 1 <= B <= nat.MAX_CELLS:
+            raise ValueError("road_cells: %d edges - 2 .. %d make 1 .. %d cells" % (len(e), nat.MAX_CELLS + 1, nat.MAX_CELLS))
+        if out is None:
+            if B not in self._cells:
+                self._cells[B] = RoadCells(torch.zeros(shape, dtype=torch.int32, device=self.device),
+                                           torch.zeros(shape, dtype=torch.float32, device=self.device))
+            out = self._cells[B]
+        else:
+            out = RoadCells(*out)
+            for name, t in zip(RoadCells._fields, out):
+                want = torch.float32 if name == "speed_sum" else torch.int32
+                if t is not None and (t.dtype != want or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                    raise ValueError("road_cells(out=): %s must be a contiguous %s [%d, %d, %d] device tensor"
+                                     % ((name, want) + shape))
+        b = nat.TfxCellBuffers()
+        b.n_cars, b.speed_sum = [_ptr(t) for t in out]
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_road_cells(self.h, e.ctypes.data_as(C.POINTER(C.c_float)), B, C.byref(b),
+                                              nat.CELLS_ACCUMULATE if accumulate else 0, self._stream()))
+        return out
+
+    def cells_launch(self, n_cells):
+        """(workgroups, wavefronts) of the road_cells launch of this engine for n_cells cells (tfx_cells_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_cells_launch(self.h, int(n_cells), C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
 
     def head_rows(self):

@@ -14,7 +14,8 @@ and return the rows of each tick next to its counts.
 
 `episode_phases` mirrors the other draw the device makes: the light phases of an env that restarts on the device
 (tfx_set_episodes, rule 2 of include/tfx.h).  `clone_plan` and `road_measures` state two more device rules in NumPy: which
-envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per road.
+envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per road.  `road_cells` does the same for
+tfx_road_cells (cars and speeds per cell of road); `cell_edges` makes the uniform edges that leave no car out.
 """
 import math
 
@@ -126,6 +127,59 @@ def road_measures(x, v, leading, lastcar, C, halt_speed=0.1, x_from=None):
         queue += unbroken & live
         total = np.where(inr, added, total)
     return cars.reshape(shape), halted.reshape(shape), queue.reshape(shape), total.reshape(shape)
+
+
+def cell_edges(length, n_cells):
+    """float32 edges [-inf, e_1 .. e_{n-1}, +inf] of n_cells equal cells of a road of `length`: e_b = float32(length * b /
+    n_cells), computed in binary64.  The outer edges are infinite, so every car is in some cell (a car that overshot the
+    road end is in the last one) and the cells of a road sum to its cars_on_roads."""
+    n_cells = int(n_cells)
+    if n_cells < 1:
+        raise ValueError("cell_edges: n_cells must be at least 1")
+    e = np.empty(n_cells + 1, np.float32)
+    e[0], e[n_cells] = -np.inf, np.inf
+    for b in range(1, n_cells):
+        e[b] = np.float32(float(length) * b / n_cells)
+    return e
+
+
+def road_cells(x, v, leading, lastcar, C, edges):
+    """The definition of tfx_road_cells (include/tfx.h) in NumPy, over ring planes: x, v float32 [..., R, C] by ring slot
+    (what tfx_export_ring produces), leading / lastcar int [..., R], edges float32 [B + 1] strictly ascending.
+    -> (n_cars int32 [..., R, B], speed_sum float32 [..., R, B]).  Car j of a road (j = 0: the head) sits in slot
+    wrap(leading + 1 + j); it is in range iff edges[0] <= x < edges[B] (a NaN x is in no cell); its cell is the number
+    of inner edges k = 1 .. B-1 with x >= edges[k] - comparisons only, a car on an edge goes to the upper cell;
+    speed_sum adds v of a cell's cars one at a time in ascending j, in float32, starting from 0 - the order the device
+    keeps, so the bits agree."""
+    C = int(C)
+    edges = np.asarray(edges, np.float32).reshape(-1)
+    B = len(edges) - 1
+    if B < 1 or np.isnan(edges).any() or not (edges[:-1] < edges[1:]).all():
+        raise ValueError("road_cells: edges must be at least two strictly ascending float32 values")
+    x = np.asarray(x, np.float32)
+    v = np.asarray(v, np.float32)
+    shape = x.shape[:-1]
+    x, v = x.reshape(-1, C), v.reshape(-1, C)
+    ld = np.asarray(leading, np.int64).reshape(-1)
+    lc = np.asarray(lastcar, np.int64).reshape(-1)
+    n = lc - ld + np.where(ld > lc, C - 1, 0)
+    rows = np.arange(len(ld))
+    cars = np.zeros((len(ld), B), np.int32)
+    total = np.zeros((len(ld), B), np.float32)
+    for j in range(C - 1):
+        live = j < n
+        slot = ld + 1 + j
+        slot = np.where(slot > C - 1, slot - (C - 1), slot)
+        slot = np.where(live, slot, 0)
+        xj, vj = x[rows, slot], v[rows, slot]
+        with np.errstate(invalid="ignore"):
+            inr = live & (xj >= edges[0]) & (xj < edges[B])
+            b = (xj[:, None] >= edges[None, 1:B]).sum(axis=1)
+            added = (total[rows, b] + vj).astype(np.float32)      # one float32 add per car
+        at = rows[inr], b[inr]
+        cars[at] += 1
+        total[at] = added[inr]
+    return cars.reshape(shape + (B,)), total.reshape(shape + (B,))
 
 
 def gap_table(cars_per_tick, tail=1e-12):

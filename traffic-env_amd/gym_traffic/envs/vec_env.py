@@ -30,13 +30,16 @@ import collections
 import numpy as np
 import torch
 
-from gym_traffic.core import TfxEngine
+from gym_traffic import devrng
+from gym_traffic.core import ARCHETYPE, TfxEngine
 from gym_traffic.envs.roadgraph import GridRoad
 from gym_traffic.spawner import ArrivalStreams
 
 
 # what TrafficVecEnv.measures() returns: the engine's four per-road tensors and the views derived from them
 VecMeasures = collections.namedtuple("VecMeasures", "n_cars n_halted queue speed_sum halted cars mean_speed pressure")
+# what TrafficVecEnv.cell_obs() returns: the engine's two per-cell tensors and the image a convolutional policy reads
+VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
 
 
 class TrafficVecEnv(object):
@@ -266,6 +269,32 @@ class TrafficVecEnv(object):
         pressure.index_add_(1, cell, n[:, :r] - n[:, nxt])
         return VecMeasures(rm.n_cars, rm.n_halted, rm.queue, rm.speed_sum, halted, cars, mean_speed,
                            pressure.view(eng.E, eng.I, 2))
+
+    def cell_obs(self, n_cells=8, edges=None, v_scale=None, accumulate=False):
+        """The discrete traffic state encoding of every env, on the device, with no host synchronisation: every approach
+        cut into cells along its length, each cell with its car count and its mean speed - one read-only launch over the
+        live cars (TfxEngine.road_cells / tfx_road_cells, include/tfx.h) plus a few torch expressions.  -> VecCells:
+            n_cars int32, speed_sum float32 [E, R, B] - per road id and cell; the engine's tensors, overwritten by the
+                        next call with the same B - or, accumulate=True, added to
+            image       float32 [E, 2, 4, B, m, n]; image.view(E, 8 * B, m, n) is the channels-first form.  Plane 0: the
+                        count of train road d * m * n + row * n + col - the approach of direction d into intersection
+                        (row, col) - at [:, 0, d, b, row, col]; plane 1: that cell's mean speed / v_scale, 0 where the
+                        cell is empty
+        edges: B + 1 ascending float32 values (default: devrng.cell_edges(length, n_cells) - B equal cells, no car left
+        out); v_scale: default the archetype's v0 (with an archetype table: the largest v0 of its rows)."""
+        eng = self.engine
+        if edges is None:
+            edges = devrng.cell_edges(float(eng.cfg.length), n_cells)
+        if v_scale is None:
+            v_scale = ARCHETYPE["car_v0"] if self.archetypes is None else float(self.archetypes[:, 4].max())
+        rc = eng.road_cells(edges, accumulate=accumulate)
+        E, B, m, n = eng.E, rc.n_cars.shape[2], eng.m, eng.n
+        cnt = rc.n_cars[:, :eng.r].view(E, 4, m, n, B).permute(0, 1, 4, 2, 3)
+        tot = rc.speed_sum[:, :eng.r].view(E, 4, m, n, B).permute(0, 1, 4, 2, 3)
+        image = torch.empty((E, 2, 4, B, m, n), dtype=torch.float32, device=eng.device)
+        image[:, 0] = cnt
+        image[:, 1] = torch.where(cnt > 0, tot / cnt.clamp(min=1) / float(v_scale), torch.zeros_like(tot))
+        return VecCells(rc.n_cars, rc.speed_sum, image)
 
     def cars_on_roads(self):
         return self.engine.cars_on_roads()
