@@ -261,6 +261,37 @@ typedef struct tfx_episode_buffers {
 } tfx_episode_buffers;
 int tfx_set_episodes(tfx_handle h, int32_t enabled, int32_t max_decisions, uint64_t seed, const tfx_episode_buffers *b);
 
+/* Warm restarts: while episodes are on (tfx_set_episodes), an env whose previous decision ended its episode restarts as
+ * a clone of an env of `pool` instead of empty.  pool == NULL detaches.  Every env of the reference's training setup is
+ * `Repeater -> WarmupWrapper(FLAGS.warmup_lights) -> Remi` (traffic_test.py:84-86): reset() runs warmup_lights decisions
+ * under sampled actions before the agent sees anything, so no episode starts on an empty map.  Here the warm-up is paid
+ * once, for the envs of a second handle (the pool), and a restart copies one of them.
+ *
+ * Rule 3 (the pool slot): global env g = env + env_id_offset, starting its episode number n (ep_index[env] as step 3 of
+ * the previous decision left it - the n of rule 2), takes env
+ *     slot = (u0 * n_pool) >> 32,  u = philox4x32(ctr = {n, g, TAG_POOL, 0}, key = seed)
+ * of the pool, n_pool = the pool handle's n_envs, seed = the one given to tfx_set_episodes, TAG_POOL = 0x504F4F4C (the
+ * other draws use 0x47415021, 0x524F4144, 0x41524348 and 0x45504953).  It depends on nothing else, so not on how envs
+ * are sharded over handles.  gym_traffic/devrng.py episode_pool_slots mirrors it.
+ *
+ * With a pool attached, step 1 of a decision does for every marked env exactly what tfx_clone_envs(h, pool, src, 0,
+ * stream) does with src[env] = slot (-1 for the other envs), in the decision's own submission and with no launch more
+ * than an episodes-on decision makes anyway: cars, counters, lights, the whole obs row (current_phase / elapsed are the
+ * pool env's: rule 2 is not drawn), caches and, in validate mode, the trip log arrive from the pool env, ticks rebased by
+ * tick(h) - tick(pool) read on the device.  The env keeps its own arrival stream and position (arrival streams run on
+ * across a restart) and its own ep_* accounting; the clone_skipped counter is not touched (a slot is always valid).
+ * Steps 2 and 3 are what they were.
+ *
+ * The pool is read, never written, and read when the restart runs: it is a pointer, not a snapshot - a caller may keep
+ * it fresh by stepping it between decisions on the same stream; work on the pool pending on ANOTHER stream is the
+ * caller's to order, as for tfx_clone_envs.  The caller keeps the pool alive (and its buffers bound) while it is
+ * attached.  Both handles bound (else TFX_ESTATE), on the same device, with the same world as tfx_clone_envs asks of
+ * dst != src (else TFX_EINVAL with a message naming the field; n_envs and env_id_offset may differ); pool == h is
+ * TFX_EINVAL.  A refused call changes nothing.  Attaching and detaching are allowed before or after tfx_set_episodes
+ * (the pool is inert while episodes are off) and re-capture the agent-step graph.  tfx_debug_fail_after counts the
+ * restart's launch like the other launches of the decision. */
+int tfx_set_episode_pool(tfx_handle h, tfx_handle pool);
+
 /* remi (traffic_env.py:64-78) via TrafficEnv.remi_reward (:384-387) */
 int tfx_remi(tfx_handle h, void *stream);
 /* cars_on_roads (traffic_env.py:214-218): out device int32 [E][R] */

@@ -15,6 +15,10 @@
 //     env's first tile writes the per-env scalars.
 // Ring layout (tfx_config.layout = 0, the non-default one): the same decomposition, each lane copies the C slots of
 // its road.
+// k_clone<true> (PICK) is the masked restart of a decision with a pool of warmed-up envs attached (tfx_set_episode_pool,
+// include/tfx.h): no index array - the wavefront reads the env's restart mark (none: it leaves on a wave-uniform branch,
+// so a decision in which nobody restarts costs one nearly empty launch) and draws the pool env by rule 3; it also does
+// k_episode_begin's other job, the `last` flags, so the decision makes no launch more than it makes without a pool.
 // A source is never written by the launch that reads it: across handles because the handles differ, in place because an
 // env whose source is itself a destination is left alone and counted (clone_plan in gym_traffic/devrng.py states the rule).
 #pragma once
@@ -35,7 +39,7 @@ struct CloneOpt {
   unsigned *d_sid, *s_sid;           // PoissonDev::sid
   unsigned *d_seq, *s_seq;           // PoissonRows::seq [E][n_entry] (heterogeneous cars), or null
   int episode;                       // the running episode's accounting
-  EpDev d_ep, s_ep;
+  EpDev d_ep, s_ep;                  // (PICK: d_ep is the destination's block whatever `episode` says - mark, ep_index, last)
   int *d_greedy, *s_greedy;          // the greedy controller's held decision [E][I], or null
   unsigned long long *skipped;       // destination handle: envs left untouched against the caller's wish
 };
@@ -70,6 +74,9 @@ __device__ __forceinline__ bool clone_allowed(const int *src_of_env, int env, in
   return t == -1 || t == s;
 }
 
+// PICK: the source of env `env` is `mark[env] ? rule 3 : -1` instead of src_of_env[env] (null then), sd the pool handle's
+// block; reads mark, ep_len and ep_index and writes none of them
+template <bool PICK>
 __global__ __launch_bounds__(256) void k_clone(const Dev dd, const Dev sd, const int *src_of_env, const CloneOpt o) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -81,13 +88,22 @@ __global__ __launch_bounds__(256) void k_clone(const Dev dd, const Dev sd, const
   for (long item = (long)blockIdx.x * 4 + wv; item < items; item += nw) {
     const int env = (int)(item / G);
     const int g = (int)(item - (long)env * G);
-    const int s = __builtin_amdgcn_readfirstlane(src_of_env[env]);
-    if (s == -1) continue;
-    if (!clone_allowed(src_of_env, env, s, sd.E, o.same != 0)) {
-      if (g == 0 && lane == 0) atomicAdd(o.skipped, 1ull);
-      continue;
+    int s;
+    if (PICK) {
+      const EpDev &ep = o.d_ep;
+      // (every env learns whether the decision under way is the last one its time limit allows, as in k_episode_begin)
+      if (g == 0 && lane == 0) ep.last[env] = (ep.max > 0 && ep.ep_len[env] + 1 == ep.max) ? 1 : 0;
+      if (__builtin_amdgcn_readfirstlane((int)ep.mark[env]) == 0) continue;
+      s = __builtin_amdgcn_readfirstlane(episode_pool_slot(ep, env, (unsigned)(env + dd.env_off), sd.E));  // always in [0, sd.E)
+    } else {
+      s = __builtin_amdgcn_readfirstlane(src_of_env[env]);
+      if (s == -1) continue;
+      if (!clone_allowed(src_of_env, env, s, sd.E, o.same != 0)) {
+        if (g == 0 && lane == 0) atomicAdd(o.skipped, 1ull);
+        continue;
+      }
+      if (o.same && s == env) continue;  // a copy of itself
     }
-    if (o.same && s == env) continue;  // a copy of itself
 
     const int e_slot = dd.slot_road[g * 64 + lane];
     const bool valid = e_slot >= 0;

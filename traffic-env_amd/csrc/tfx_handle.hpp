@@ -127,6 +127,8 @@ struct tfx_handle_s {
   // episodes on the device (tfx_set_episodes): the parameter block, and its copy on the device (k_res reads it through a pointer)
   EpDev ep{};
   EpDev *dev_ep = nullptr;
+  // warm restarts (tfx_set_episode_pool): the handle whose envs a restart clones, or null; the caller keeps it alive
+  tfx_handle_s *pool = nullptr;
   // tfx_clone_envs (tfx_clone.hpp): the device the handle lives on, the rate its Poisson stream was set up with (two
   // handles must run the same stream to share one), the stream ids of its envs, the counter of envs left untouched
   int device = 0;

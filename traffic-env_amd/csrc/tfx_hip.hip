@@ -35,6 +35,16 @@ void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const v
            (void *)d.done_tick, h->ep.on, h->ep.max, h->ep.seed_lo, h->ep.seed_hi, (void *)h->ep.ep_return,
            (void *)h->ep.ep_len, (void *)h->ep.final_return, (void *)h->ep.final_len, (void *)h->ep.trunc,
            (void *)h->ep.ep_index);
+  // warm restarts (tfx_set_episode_pool): the pool's block is baked into the restart's arguments - whatever of it a
+  // caller can re-bind (the rest lives as long as the pool handle does)
+  if (const tfx_handle p = h->pool) {
+    const size_t used = strlen(key);
+    const Dev &s = p->d;
+    snprintf(key + used, n - used, "|%p|%p|%p|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%p", (void *)p, (void *)s.xv, (void *)s.w,
+             (void *)s.obs, (void *)s.leading, (void *)s.lastcar, (void *)s.rewards, (void *)s.waiting,
+             (void *)s.passed_dst, (void *)s.done_tick, (void *)s.n_trips, (void *)s.trip_times, s.trip_cap,
+             (void *)s.greedy_act);
+  }
 }
 
 }  // namespace
@@ -68,7 +78,7 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
     return rc;
   }
   // one graph per distinct launch sequence: everything baked into kernel arguments is in the key
-  char key[896];
+  char key[1280];
   graph_key(h, key, sizeof key, n_ticks, remi, aobs, areward, adone);
   if (!h->ag_exec || h->ag_key != key) {
     if (h->ag_exec) { (void)hipGraphExecDestroy(h->ag_exec); h->ag_exec = nullptr; }
@@ -139,7 +149,7 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
 
 // the same as a captured graph: captured once per distinct sequence (graph_key), replayed afterwards
 int step_graph(tfx_handle h, int n_ticks, hipStream_t st) {
-  char key[896];
+  char key[1280];
   graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
   if (!h->st_exec || h->st_key != key) {
     if (h->st_exec) { (void)hipGraphExecDestroy(h->st_exec); h->st_exec = nullptr; }
@@ -956,34 +966,49 @@ int tfx_split_ticks(tfx_handle h, int64_t *ticks) {
 
 const char *tfx_step_kernel(tfx_handle h) { return h ? h->step_kernel : ""; }
 
+}  // extern "C"
+
+namespace {
+
+// Two handles a clone can go between (tfx_clone_envs with dst != src, tfx_set_episode_pool): the same device and the
+// same world; anything else is TFX_EINVAL with a message naming the field, led by `what`
+int same_world(tfx_handle dst, tfx_handle src, const char *what) {
+  const tfx_config &a = dst->cfg, &b = src->cfg;
+  if (dst->device != src->device)
+    return fail(TFX_EINVAL, "%s: the handles live on different devices (device %d / %d)", what, dst->device, src->device);
+#define TFX_SAME(field, fmt)                                                                                         \
+  if (a.field != b.field) return fail(TFX_EINVAL, "%s: the handles differ in " #field " (" fmt " / " fmt ")", what, a.field, b.field)
+  TFX_SAME(m, "%d"); TFX_SAME(n, "%d"); TFX_SAME(capacity, "%d"); TFX_SAME(planes, "%d"); TFX_SAME(layout, "%d");
+  TFX_SAME(length, "%g"); TFX_SAME(rate, "%g"); TFX_SAME(validate, "%d"); TFX_SAME(learn_switch, "%d");
+  TFX_SAME(entry_spec, "%u");
+  // (the constants every tick reads: a clone continues as its source does only under the same ones)
+  TFX_SAME(yellow_ticks, "%d"); TFX_SAME(thresh, "%g"); TFX_SAME(detect_dist, "%g"); TFX_SAME(overflow_penalty, "%g");
+  TFX_SAME(eps, "%g");
+#undef TFX_SAME
+  if (dst->het != src->het || dst->n_arch != src->n_arch)
+    return fail(TFX_EINVAL, "%s: the handles differ in n_archetypes (%d / %d rows)", what, dst->n_arch, src->n_arch);
+  const bool table = a.n_archetypes >= 1;
+  if (table != (b.n_archetypes >= 1) ||
+      (table ? memcmp(a.arch, b.arch, (size_t)dst->n_arch * sizeof a.arch[0]) != 0
+             : (a.car_v != b.car_v || a.car_l != b.car_l || a.car_a != b.car_a || a.car_delta != b.car_delta ||
+                a.car_v0 != b.car_v0 || a.car_b != b.car_b || a.car_T != b.car_T || a.car_s0 != b.car_s0)))
+    return fail(TFX_EINVAL, "%s: the handles differ in the archetype table (arch)", what);
+  if (dst->h_slot_road != src->h_slot_road)
+    return fail(TFX_EINVAL, "%s: the handles differ in the kinds ordering of their storage slots (TFX_KINDS)", what);
+  return TFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, int32_t flags, void *stream) {
   if (flags & ~(TFX_CLONE_STREAM | TFX_CLONE_EPISODE)) return fail(TFX_EINVAL, "unknown clone flags 0x%x", flags);
   if (!src_of_env) return fail(TFX_EINVAL, "src_of_env is null");
   if (int rc = check_handle(dst, true)) return rc;
   if (int rc = check_handle(src, true)) return rc;
-  const tfx_config &a = dst->cfg, &b = src->cfg;
   if (dst != src) {
-    if (dst->device != src->device)
-      return fail(TFX_EINVAL, "clone: the handles live on different devices (device %d / %d)", dst->device, src->device);
-#define TFX_SAME(field, fmt)                                                                                         \
-  if (a.field != b.field) return fail(TFX_EINVAL, "clone: the handles differ in " #field " (" fmt " / " fmt ")", a.field, b.field)
-    TFX_SAME(m, "%d"); TFX_SAME(n, "%d"); TFX_SAME(capacity, "%d"); TFX_SAME(planes, "%d"); TFX_SAME(layout, "%d");
-    TFX_SAME(length, "%g"); TFX_SAME(rate, "%g"); TFX_SAME(validate, "%d"); TFX_SAME(learn_switch, "%d");
-    TFX_SAME(entry_spec, "%u");
-    // (the constants every tick reads: a clone continues as its source does only under the same ones)
-    TFX_SAME(yellow_ticks, "%d"); TFX_SAME(thresh, "%g"); TFX_SAME(detect_dist, "%g"); TFX_SAME(overflow_penalty, "%g");
-    TFX_SAME(eps, "%g");
-#undef TFX_SAME
-    if (dst->het != src->het || dst->n_arch != src->n_arch)
-      return fail(TFX_EINVAL, "clone: the handles differ in n_archetypes (%d / %d rows)", dst->n_arch, src->n_arch);
-    const bool table = a.n_archetypes >= 1;
-    if (table != (b.n_archetypes >= 1) ||
-        (table ? memcmp(a.arch, b.arch, (size_t)dst->n_arch * sizeof a.arch[0]) != 0
-               : (a.car_v != b.car_v || a.car_l != b.car_l || a.car_a != b.car_a || a.car_delta != b.car_delta ||
-                  a.car_v0 != b.car_v0 || a.car_b != b.car_b || a.car_T != b.car_T || a.car_s0 != b.car_s0)))
-      return fail(TFX_EINVAL, "clone: the handles differ in the archetype table (arch)");
-    if (dst->h_slot_road != src->h_slot_road)
-      return fail(TFX_EINVAL, "clone: the handles differ in the kinds ordering of their storage slots (TFX_KINDS)");
+    if (int rc = same_world(dst, src, "clone")) return rc;
   }
   CloneOpt o{};
   o.same = dst == src ? 1 : 0;
@@ -1019,14 +1044,23 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
     o.s_greedy = src->d.greedy_act;
   }
   TFX_INJECT(dst);
-  // a wavefront per (destination env, tile), four to a workgroup; a few workgroups per compute unit stride over more
-  const long items = (long)dst->d.E * dst->d.G;
-  long grid = (items + 3) / 4;
-  const long cap = (long)dst->n_cu * 16;
-  if (grid > cap) grid = cap;
-  hipLaunchKernelGGL(k_clone, dim3((unsigned)(grid < 1 ? 1 : grid)), dim3(256), 0, (hipStream_t)stream, dst->d, src->d,
+  hipLaunchKernelGGL(k_clone<false>, dim3(clone_grid(dst)), dim3(256), 0, (hipStream_t)stream, dst->d, src->d,
                      (const int *)src_of_env, o);
   HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_set_episode_pool(tfx_handle h, tfx_handle pool) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (pool == h) return fail(TFX_EINVAL, "episode pool: a handle cannot be its own pool");
+  if (int rc = check_handle(h, true)) return rc;
+  if (pool) {
+    if (int rc = check_handle(pool, true)) return rc;
+    if (int rc = same_world(h, pool, "episode pool")) return rc;
+  }
+  // (nothing on the device changes: decisions under way keep the arguments they were enqueued with)
+  h->pool = pool;
+  ++h->input_gen;  // the captured agent-step graph holds the other form of the restart
   return TFX_OK;
 }
 

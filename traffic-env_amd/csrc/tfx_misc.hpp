@@ -218,6 +218,7 @@ struct PoissonRows {
 };
 constexpr unsigned TAG_ARCH = 0x41524348u;  // (TAG_GAP / TAG_ROAD: 0x47415021 / 0x524F4144, gym_traffic/devrng.py)
 constexpr unsigned TAG_EPISODE = 0x45504953u;  // rule 2 of include/tfx.h
+constexpr unsigned TAG_POOL = 0x504F4F4Cu;     // rule 3 of include/tfx.h
 
 // Begin of a decision with episodes on (tfx_set_episodes), one launch ahead of the ticks: the envs whose last decision
 // ended their episode (mark, left by that decision's tail) restart as k_reset would restart them, the phase of
@@ -241,6 +242,15 @@ __global__ void k_episode_begin(const Dev d, const EpDev ep) {
     }
     reset_road(d, env, e, id, phase);
   }
+}
+
+// Rule 3 of include/tfx.h (tfx_set_episode_pool): the env of a pool of n_pool warmed-up envs that global env g restarts
+// from at the start of its episode number ep_index[env] - (u0 * n_pool) >> 32 of philox4x32({episode number, g, TAG_POOL,
+// 0}, seed).  gym_traffic/devrng.py episode_pool_slots mirrors it.
+__device__ __forceinline__ int episode_pool_slot(const EpDev &ep, const int env, const unsigned g, const int n_pool) {
+  unsigned u[4];
+  philox4x32((unsigned)ep.ep_index[env], g, TAG_POOL, 0u, ep.seed_lo, ep.seed_hi, u);
+  return (int)(((unsigned long long)u[0] * (unsigned)n_pool) >> 32);
 }
 
 // End of a decision with episodes on, for intersection gi of env `env` / for the env itself (include/tfx.h, step 3);

@@ -1,9 +1,36 @@
 // tfx_sequence.hpp - the launch sequences of tfx_step and tfx_agent_step: pairs of ticks, the env range in two halves on
 // two streams, the agent step (host side; included by tfx_hip.hip).
 #pragma once
+#include "tfx_clone.hpp"
 #include "tfx_launch.hpp"
 
 namespace {
+
+// workgroups of a k_clone launch: a wavefront per (destination env, tile), four to a workgroup; a few workgroups per
+// compute unit stride over more
+unsigned clone_grid(tfx_handle dst) {
+  const long items = (long)dst->d.E * dst->d.G;
+  long grid = (items + 3) / 4;
+  const long cap = (long)dst->n_cu * 16;
+  if (grid > cap) grid = cap;
+  return (unsigned)(grid < 1 ? 1 : grid);
+}
+
+// The masked restart of a decision from the attached pool (tfx_set_episode_pool): what tfx_clone_envs(h, pool, src, 0)
+// does with src[env] = the slot of rule 3 for the marked envs and -1 for the others, the source picked in the kernel
+// (k_clone<true>, which also leaves the `last` flags behind) - the pool as it is when the launch runs
+int launch_pool_restart(tfx_handle h, hipStream_t st) {
+  const tfx_handle pool = h->pool;
+  CloneOpt o{};
+  o.d_ep = h->ep;
+  if (h->d.greedy_act && pool->d.greedy_act) {
+    o.d_greedy = h->d.greedy_act;
+    o.s_greedy = pool->d.greedy_act;
+  }
+  hipLaunchKernelGGL(k_clone<true>, dim3(clone_grid(h)), dim3(256), 0, st, h->d, pool->d, (const int *)nullptr, o);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
 
 // the second stream of a split call and the events that fork it from / join it to the caller's stream.
 // The second stream must not share a hardware queue with the caller's: HIP hands its hardware queues (4 per priority
@@ -81,8 +108,13 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
     // episodes (tfx_set_episodes): the envs whose last decision ended their episode restart, ahead of the ticks and
     // of any fork - the one launch the feature adds; the accounting rides in the decision's tail
     TFX_INJECT(h);
-    hipLaunchKernelGGL(k_episode_begin, dim3(grid_for((long)d.E * d.R, h->n_cu)), dim3(256), 0, st, d, h->ep);
-    HIPCHK(hipGetLastError());
+    if (h->pool) {
+      // ... as clones of envs of the attached pool (tfx_set_episode_pool), in that same one launch
+      if (int rc = launch_pool_restart(h, st)) return rc;
+    } else {
+      hipLaunchKernelGGL(k_episode_begin, dim3(grid_for((long)d.E * d.R, h->n_cu)), dim3(256), 0, st, d, h->ep);
+      HIPCHK(hipGetLastError());
+    }
   }
   if (res_usable(h, n_ticks)) {
     // every tick of the decision AND its tail (remi, observation, rewards, done flags) in one launch

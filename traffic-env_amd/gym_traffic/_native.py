@@ -67,6 +67,7 @@ _PROTOS = {
     "tfx_reset_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfx_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tfx_set_episodes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(TfxEpisodeBuffers)]),
+    "tfx_set_episode_pool": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tfx_set_actions": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "tfx_set_spawns": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "tfx_set_poisson": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_void_p, C.c_int32]),

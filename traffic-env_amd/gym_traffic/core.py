@@ -211,6 +211,7 @@ class TfxEngine(object):
         self.tick = 0
         # episodes on the device (set_episodes): None while off
         self.ep_return = self.ep_len = self.final_return = self.final_len = self.truncated = self.ep_index = None
+        self.episode_pool = None    # the engine restarts clone from (set_episode_pool)
         # views with the reference's attribute names (traffic_env.py:372-376)
         self.passed = self.obs[:, :r]
         self.detected = self.obs[:, r:2 * r]
@@ -349,6 +350,16 @@ class TfxEngine(object):
         with torch.cuda.device(dev):
             nat.check(self.lib.tfx_set_episodes(self.h, 1, limit, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(b)))
         self._ep_keep = b
+
+    def set_episode_pool(self, pool):
+        """Warm restarts (tfx_set_episode_pool, include/tfx.h): while episodes are on, an env that ended restarts as a
+        clone of an env of `pool` - another engine of the same world, warmed up by the caller - instead of empty; which
+        one is rule 3 (devrng.episode_pool_slots).  The restart is clone_envs(..., streams=False, episodes=False) for the
+        envs that ended, inside the decision's submission; the pool is read when the restart runs, never written.  None
+        detaches.  The engine keeps a reference to the pool while it is attached."""
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_set_episode_pool(self.h, None if pool is None else pool.h))
+        self.episode_pool = pool
 
     def clone_envs(self, src_of_env, source=None, streams=False, episodes=False):
         """Env e becomes a copy of env src_of_env[e] of `source` (another engine of the same world; default: this

@@ -25,6 +25,7 @@ M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 TAG_GAP, TAG_ROAD, TAG_ARCH = 0x47415021, 0x524F4144, 0x41524348
 TAG_EPISODE = 0x45504953
+TAG_POOL = 0x504F4F4C
 MASK = 0xFFFFFFFF
 
 
@@ -68,6 +69,18 @@ def episode_phases(seed, env_ids, ep_index, I):
     u0 = philox4x32_first(np.broadcast_to(n[:, None], shape), np.broadcast_to(env_ids[:, None], shape), TAG_EPISODE,
                           np.broadcast_to(np.arange(int(I), dtype=np.uint64)[None, :], shape), seed & MASK, seed >> 32)
     return (u0 & np.uint64(1)).astype(np.int32)
+
+
+def episode_pool_slots(seed, env_ids, ep_index, n_pool):
+    """int32 [len(env_ids)]: the env of a pool of `n_pool` warmed-up envs that global envs `env_ids` restart from at the
+    start of their episode number `ep_index` (a scalar or one per env) - rule 3 of include/tfx.h (tfx_set_episode_pool):
+    (u0 * n_pool) >> 32 with u0 the first word of philox4x32({episode number, global env id, TAG_POOL, 0}, key = seed).
+    A pure function of (seed, global env id, episode number, n_pool)."""
+    env_ids = np.asarray(env_ids, np.uint64).reshape(-1)
+    n = np.zeros_like(env_ids) + (np.asarray(ep_index, np.int64).astype(np.uint64) & np.uint64(MASK))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    u0 = philox4x32_first(n, env_ids, TAG_POOL, 0, seed & MASK, seed >> 32)
+    return ((u0 * np.uint64(int(n_pool))) >> np.uint64(32)).astype(np.int32)
 
 
 def clone_plan(src_of_env, n_src=None):

@@ -24,6 +24,13 @@ algorithms/greedy.py:13) - with phases drawn on the device, and accounts for the
 `episode_length` (running), `final_return`, `final_length` (of the episode that just ended; valid where
 `adone | truncated`).  The observation returned for an env that ended is its terminal one; its new episode starts with
 the next decision.  No host work per decision; `reset_done()` is not to be called in this mode.
+
+Warm restarts: every env of the reference's training setup is `Repeater -> WarmupWrapper(FLAGS.warmup_lights) -> Remi`
+(traffic_test.py:84-86) - reset() runs warmup_lights decisions under sampled actions before the agent sees anything, so
+no episode starts on an empty map.  `make_warm_pool` pays that warm-up once, for a small second TrafficVecEnv, and
+`set_warm_pool` attaches it: from then on a restart on the device is a clone of one of the pool's envs (which one: rule 3
+of include/tfx.h, devrng.episode_pool_slots) instead of an empty map, still inside the decision's one submission;
+`reset(warm=True)` starts episode 0 the same way.
 """
 import collections
 
@@ -108,12 +115,67 @@ class TrafficVecEnv(object):
     def observation_shape(self):
         return (self.num_envs, self.engine.obs_len)
 
-    def reset(self, phase_init=None):
+    def reset(self, phase_init=None, warm=False):
+        """warm: with a pool attached (set_warm_pool), after the plain reset every env becomes a clone of the pool env
+        devrng.episode_pool_slots(seed, global env ids, episode_index, pool size) names - rule 3 with the episode numbers
+        the reset left (0 after construction) - so the first episode starts as warm as the later ones; the envs keep
+        their own arrival streams and accounting."""
         eng = self.engine
         if phase_init is None:
             phase_init = self._phase_rng.randint(2, size=(eng.E, eng.I)).astype(np.int32)
         eng.reset(phase_init)
+        if warm:
+            pool = self.warm_pool
+            if pool is None:
+                raise RuntimeError("reset(warm=True) needs a pool of warmed-up envs: set_warm_pool(make_warm_pool(...))")
+            ids = np.arange(self.num_envs) + self.env_id_offset
+            slots = devrng.episode_pool_slots(self._ctor["seed"], ids, self.episode_index.cpu().numpy(), pool.num_envs)
+            self.clone_envs(slots, source=pool, streams=False, episodes=False)
         return eng.obs
+
+    # ---- warm restarts (tfx_set_episode_pool, include/tfx.h) ---------------------------------------------------------
+    warm_pool = None
+    # global env ids from here on are the pools' (make_warm_pool's default): their arrival streams stay apart from the
+    # live envs' however those are sharded, and every shard that builds its pool with the default builds the same one
+    POOL_ENV_ID_OFFSET = 1 << 30
+
+    def set_warm_pool(self, pool):
+        """Attach `pool` (a TrafficVecEnv of the same world, e.g. from make_warm_pool; None detaches): the envs that end
+        restart on the device as clones of its envs instead of empty.  The pool is read at the time of each restart and
+        never written - step it between decisions to keep it fresh.  Kept alive by this env while attached."""
+        if not self.autoreset:
+            raise RuntimeError("set_warm_pool() needs autoreset=True (the restarts it warms are those on the device)")
+        self.engine.set_episode_pool(None if pool is None else pool.engine)
+        self.warm_pool = pool
+
+    def make_warm_pool(self, n_pool, decisions, n_ticks=10, cycle_period=None, seed=None, env_id_offset=None):
+        """A TrafficVecEnv of n_pool envs of this env's construction (autoreset off), reset and run through `decisions`
+        agent decisions of n_ticks ticks - WarmupWrapper's reset (wrappers/warmup.py:8-13): actions sampled per light from
+        a torch generator on the device seeded `seed` (default: this env's seed), or the fixed cycle with cycle_period.
+        env_id_offset (default POOL_ENV_ID_OFFSET = 2**30) keeps the pool's arrival streams apart from the live envs'.
+        Raises RuntimeError("Episode completed during warmup") if an env overflowed, as the reference asserts.  In
+        validate mode the pool's n_trips are zeroed: warm-up trips do not enter the live envs' logs.  Returns the pool;
+        attach it with set_warm_pool."""
+        ctor = dict(self._ctor, autoreset=False, episode_len=None,
+                    env_id_offset=self.POOL_ENV_ID_OFFSET if env_id_offset is None else int(env_id_offset))
+        pool = TrafficVecEnv(int(n_pool), **ctor)
+        pool.reset()
+        eng = pool.engine
+        gen = torch.Generator(device=eng.device)
+        gen.manual_seed(int(self._ctor["seed"] if seed is None else seed))
+        over = torch.zeros_like(eng.done)
+        for _ in range(int(decisions)):
+            if cycle_period is not None:
+                out = pool.agent_step(n_ticks=n_ticks, cycle_period=cycle_period)
+            else:
+                act = torch.randint(0, 2, (eng.E, eng.I), generator=gen, device=eng.device, dtype=torch.int32)
+                out = pool.agent_step(act, n_ticks=n_ticks)
+            over |= out[2]
+        if bool(over.any()):
+            raise RuntimeError("Episode completed during warmup")
+        if eng.n_trips is not None:
+            eng.n_trips.zero_()
+        return pool
 
     def reset_done(self, done=None, phase_init=None):
         """Start a new episode in the envs that are done (default: the `done` flags of the last step
