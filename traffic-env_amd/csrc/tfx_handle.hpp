@@ -1,5 +1,6 @@
 // tfx_handle.hpp - the handle behind the C ABI (include/tfx.h): configuration, device parameter block, launch
-// geometry, optional per-kernel timing, the tables of GridRoad (roadgraph.py:26-64) and the storage-slot order.
+// geometry (filled by size_grids, tfx_launch.hpp), the captured launch sequences, optional per-kernel timing, the
+// tables of GridRoad (roadgraph.py:26-64) and the storage-slot order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,12 +40,25 @@ int fail(int code, const char *fmt, ...) {
 
 }  // namespace
 
+// A launch sequence captured as a HIP graph (run_captured, tfx_hip.hip): the graph, the key of everything baked into
+// its kernel arguments (graph_key), and what ONE replay does to the handle - the ticks it adds to the counters and the
+// kernel its last mover reports (tfx_step_kernel).
+struct CapturedSeq {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  std::string key;
+  long long fused = 0, pair = 0, tail = 0;
+  const char *step_kernel = "";
+};
+enum { SEQ_AGENT = 0, SEQ_STEP = 1 };  // tfx_agent_step's decision, a tfx_step call of a launch-bound handle
+
 struct tfx_handle_s {
   tfx_config cfg;
   Dev d;
   bool bound = false;
   int n_cu = 256;
   int wpr = 1;
+  // grids: 0 = not sized yet (size_grids, at the entry of the first API call that can launch the kernel)
   int grid_move = 0;
   int grid_tt[4] = {0, 0, 0, 0};  // k_move_tt<false>, <true>, <false, agent>, <true, agent>
   int grid_edge = 0;
@@ -89,29 +103,22 @@ struct tfx_handle_s {
   long long fused_ticks = 0;   // ticks run by k_res since tfx_create
   long long pair_ticks = 0;    // ticks run as two-tick passes since tfx_create
   long long tail_ticks = 0;    // ... of which k_tail finished the pair (tfx_tail.hpp)
-  long long ag_fused = 0, ag_pair = 0;  // what ONE replay of the captured agent-step graph adds to the two above
   const char *step_kernel = "";  // the kernel that moved the cars in the last tick (tfx_step_kernel)
-  // TFX_MOVE_VARIANT selects the move kernel for A/B runs (see launch_move); 0 = best known
+  // TFX_MOVE_VARIANT selects the move kernel for A/B runs (see pick_move); 0 = best known
   int move_variant = 0;
-  size_t move_lds = 0;
+  int move_blocks_per_cu = 0;  // TFX_MOVE_BLOCKS_PER_CU: workgroups per CU of the move kernels' grids (0: as measured)
+  bool stagger = true;         // TFX_STAGGER=0: the second half's first pass does not wait for the first half's
   unsigned long long div_mismatches = 0;  // result of the reciprocal-division self-test
   size_t n_tpairs = 0;                    // (x, v) pairs the xv buffer must hold in the transposed layout
-  // fused agent step: the launch sequence of one step, captured once per (ticks, remi, inputs)
-  hipGraph_t ag_graph = nullptr;
-  hipGraphExec_t ag_exec = nullptr;
+  // fused agent step: the launch sequence of one step, captured once per (ticks, remi, inputs); tfx_step calls of
+  // launch-bound handles replay a captured graph as well (tfx_hip.hip).  Both are captured on ag_stream.
+  CapturedSeq captured[2];  // SEQ_AGENT, SEQ_STEP
   hipStream_t ag_stream = nullptr;
-  std::string ag_key;
-  // tfx_step calls of launch-bound handles replay a captured graph as well (step_graph, tfx_hip.hip)
-  hipGraph_t st_graph = nullptr;
-  hipGraphExec_t st_exec = nullptr;
-  std::string st_key;
-  long long st_pair = 0, st_tail = 0;  // what one replay adds to pair_ticks / tail_ticks
   // bumped by every call that changes something a captured kernel argument was built from (bound
   // buffers, action / spawn rules, the Poisson stream): part of the graph key, so a stale graph is
   // never replayed even when a re-allocated buffer lands on the address the old one had
   unsigned long long input_gen = 0;
   bool use_graph = true;  // TFX_GRAPH=0 disables
-  bool size_only = false;
   int fail_after = 0;  // tfx_debug_fail_after: the n-th launch from now fails (error-path tests); 0 = off
   // on-device Poisson arrivals / greedy controller (own buffers)
   bool poisson = false, greedy = false;
@@ -203,7 +210,7 @@ void build_slots(tfx_handle_s *h) {
 
 // fault injection for the error-path tests (tfx_debug_fail_after): true when THIS launch is the one to fail
 bool inject_failure(tfx_handle h) {
-  if (h->size_only || h->fail_after <= 0) return false;
+  if (h->fail_after <= 0) return false;
   return --h->fail_after == 0;
 }
 #define TFX_INJECT(h)                                                                              \

@@ -10,7 +10,7 @@
 //     with the env range in two halves on two streams (tfx_sequence.hpp; validate mode: the W forms of both kernels,
 //     heterogeneous cars: the HET forms); small launches and the ring layout: k_move_t / k_move_ts / k_move_dma /
 //     k_move<WPR> + k_advance.
-// This file is the C ABI itself; the handle is in tfx_handle.hpp, kernel choice and launch geometry in tfx_launch.hpp,
+// This file is the C ABI itself; the handle is in tfx_handle.hpp, kernel choice, grid sizing and launches in tfx_launch.hpp,
 // the launch sequences of tfx_step / tfx_agent_step in tfx_sequence.hpp, the cold kernels in tfx_misc.hpp.
 #include <cmath>
 #include <new>
@@ -47,6 +47,45 @@ void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const v
   }
 }
 
+
+// One captured sequence through its whole cycle: capture `body` (which enqueues on the stream it is given) when the key
+// differs from that of the graph at hand, then replay the graph on `st`.  The grids were sized at the API entry: no
+// occupancy query or function attribute may run between the begin and the end of a capture (size_grids).
+// Counting: a body adds the ticks it enqueues to the handle's counters, as it does when it runs eagerly.  A capture ran
+// no kernel, so what the body added is taken back, kept as the sequence's per-replay addition, and every replay -
+// the first included - adds it again and reports the capture's last mover.
+template <class Body>
+int run_captured(tfx_handle h, CapturedSeq &c, const char *key, hipStream_t st, Body body) {
+  if (!c.exec || c.key != key) {
+    if (c.exec) { (void)hipGraphExecDestroy(c.exec); c.exec = nullptr; }
+    if (c.graph) { (void)hipGraphDestroy(c.graph); c.graph = nullptr; }
+    if (!h->ag_stream) HIPCHK(hipStreamCreateWithFlags(&h->ag_stream, hipStreamNonBlocking));
+    const long long fused0 = h->fused_ticks, pair0 = h->pair_ticks, tail0 = h->tail_ticks;
+    HIPCHK(hipStreamBeginCapture(h->ag_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = body(h->ag_stream);
+    hipGraph_t g = nullptr;
+    const hipError_t ce = hipStreamEndCapture(h->ag_stream, &g);
+    c.fused = h->fused_ticks - fused0;
+    c.pair = h->pair_ticks - pair0;
+    c.tail = h->tail_ticks - tail0;
+    c.step_kernel = h->step_kernel;
+    h->fused_ticks = fused0;
+    h->pair_ticks = pair0;
+    h->tail_ticks = tail0;
+    if (rc != TFX_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (ce != hipSuccess) return fail(TFX_EDEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+    c.graph = g;
+    HIPCHK(hipGraphInstantiate(&c.exec, g, nullptr, nullptr, 0));
+    c.key = key;
+  }
+  HIPCHK(hipGraphLaunch(c.exec, st));
+  h->fused_ticks += c.fused;
+  h->pair_ticks += c.pair;
+  h->tail_ticks += c.tail;
+  h->step_kernel = c.step_kernel;
+  return TFX_OK;
+}
+
 }  // namespace
 
 extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float *aobs, float *areward,
@@ -57,7 +96,9 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
     return fail(TFX_EINVAL, "the fused agent step holds ONE action for all its ticks (bind the action buffer "
                             "with per_tick = 0)");
   hipStream_t st = (hipStream_t)stream;
-  (void)h->d;
+  if (!res_usable(h, n_ticks)) {
+    if (int rc = size_grids(h, true, n_ticks)) return rc;
+  }
   // a batch whose halves still fill the chip: two halves on two streams (k_tail of one under the pass of the other)
   // (decisions split later than plain calls: fused 10-tick decisions at cfg2, us, two halves / one range - the captured
   // graph: 384 envs 715 / 687, 448 747 / 726, 512 808 / 796-807, 768 1064 / 1019-1064, 1024 1251 / 1256, 4096 4380 / 4500 -
@@ -67,53 +108,13 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
   if (split) {
     if (int rc = ensure_split(h, st)) return rc;
   }
-  if (!h->use_graph || split) {
-    long long nf = 0, np = 0;
-    const int rc = agent_sequence(h, n_ticks, remi, aobs, areward, adone, st, nf, np, split);
-    if (rc == TFX_OK) {
-      h->fused_ticks += nf;
-      h->pair_ticks += np;
-      if (split) h->split_ticks += n_ticks;
-    }
-    return rc;
-  }
+  if (!h->use_graph || split) return agent_sequence(h, n_ticks, remi, aobs, areward, adone, st, split);
   // one graph per distinct launch sequence: everything baked into kernel arguments is in the key
   char key[1280];
   graph_key(h, key, sizeof key, n_ticks, remi, aobs, areward, adone);
-  if (!h->ag_exec || h->ag_key != key) {
-    if (h->ag_exec) { (void)hipGraphExecDestroy(h->ag_exec); h->ag_exec = nullptr; }
-    if (h->ag_graph) { (void)hipGraphDestroy(h->ag_graph); h->ag_graph = nullptr; }
-    if (!h->ag_stream) HIPCHK(hipStreamCreateWithFlags(&h->ag_stream, hipStreamNonBlocking));
-    if (h->grid_move == 0 && !res_usable(h, n_ticks)) {  // size the move grid outside the capture (occupancy queries)
-      if (int rc = launch_move_probe(h)) return rc;
-    }
-    if (!res_usable(h, n_ticks) && h->grid_adv == 0) {
-      h->size_only = true;
-      (void)launch_advance(h, 0, nullptr);
-      h->size_only = false;
-    }
-    if (!res_usable(h, n_ticks) && pairs_usable(h)) {
-      h->size_only = true;
-      (void)launch_move_tt<true, true>(h, 0, nullptr);
-      (void)launch_move_tt<false, true>(h, 0, nullptr);
-      if (tail_usable(h)) (void)launch_tail(h, 0, nullptr, true);
-      h->size_only = false;
-      (void)edge_grid(h);
-    }
-    HIPCHK(hipStreamBeginCapture(h->ag_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = agent_sequence(h, n_ticks, remi, aobs, areward, adone, h->ag_stream, h->ag_fused, h->ag_pair);
-    hipGraph_t g = nullptr;
-    const hipError_t ce = hipStreamEndCapture(h->ag_stream, &g);
-    if (rc != TFX_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (ce != hipSuccess) return fail(TFX_EDEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-    h->ag_graph = g;
-    HIPCHK(hipGraphInstantiate(&h->ag_exec, g, nullptr, nullptr, 0));
-    h->ag_key = key;
-  }
-  HIPCHK(hipGraphLaunch(h->ag_exec, st));
-  h->fused_ticks += h->ag_fused;  // (the capture ran no kernel: every replay counts)
-  h->pair_ticks += h->ag_pair;
-  return TFX_OK;
+  return run_captured(h, h->captured[SEQ_AGENT], key, st, [&](hipStream_t cs) {
+    return agent_sequence(h, n_ticks, remi, aobs, areward, adone, cs);
+  });
 }
 
 namespace {
@@ -145,48 +146,6 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
     return rc;
   }
   return step_chunk(h, n_ticks, st);
-}
-
-// the same as a captured graph: captured once per distinct sequence (graph_key), replayed afterwards
-int step_graph(tfx_handle h, int n_ticks, hipStream_t st) {
-  char key[1280];
-  graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
-  if (!h->st_exec || h->st_key != key) {
-    if (h->st_exec) { (void)hipGraphExecDestroy(h->st_exec); h->st_exec = nullptr; }
-    if (h->st_graph) { (void)hipGraphDestroy(h->st_graph); h->st_graph = nullptr; }
-    if (!h->ag_stream) HIPCHK(hipStreamCreateWithFlags(&h->ag_stream, hipStreamNonBlocking));
-    // grids are sized outside the capture (occupancy queries, function attributes)
-    h->size_only = true;
-    (void)launch_advance(h, 0, nullptr);
-    if (pairs_usable(h)) {
-      (void)launch_move_tt<true>(h, 0, nullptr);
-      (void)launch_move_tt<false>(h, 0, nullptr);
-      if (single_tick_ts(h)) (void)launch_move(h, 0, nullptr);  // (a call's odd last tick)
-      if (tail_usable(h)) (void)launch_tail(h, 0, nullptr);
-    } else {
-      (void)launch_move(h, 0, nullptr);
-    }
-    h->size_only = false;
-    if (pairs_usable(h)) (void)edge_grid(h);
-    const long long pair0 = h->pair_ticks, tail0 = h->tail_ticks;
-    HIPCHK(hipStreamBeginCapture(h->ag_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = step_body(h, n_ticks, h->ag_stream);
-    hipGraph_t g = nullptr;
-    const hipError_t ce = hipStreamEndCapture(h->ag_stream, &g);
-    h->st_pair = h->pair_ticks - pair0;  // (the capture ran no kernel: every replay counts, see below)
-    h->st_tail = h->tail_ticks - tail0;
-    h->pair_ticks = pair0;
-    h->tail_ticks = tail0;
-    if (rc != TFX_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (ce != hipSuccess) return fail(TFX_EDEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-    h->st_graph = g;
-    HIPCHK(hipGraphInstantiate(&h->st_exec, g, nullptr, nullptr, 0));
-    h->st_key = key;
-  }
-  HIPCHK(hipGraphLaunch(h->st_exec, st));
-  h->pair_ticks += h->st_pair;
-  h->tail_ticks += h->st_tail;
-  return TFX_OK;
 }
 
 }  // namespace
@@ -246,6 +205,8 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   if (const char *gv = getenv("TFX_TT_SEG")) h->tt_seg = atoi(gv);
   if (const char *gv = getenv("TFX_TT_SEGS")) h->tt_segs = atoi(gv);
   if (const char *gv = getenv("TFX_MEASURE_GRID")) h->measure_grid = atoi(gv);
+  if (const char *pc = getenv("TFX_MOVE_BLOCKS_PER_CU")) h->move_blocks_per_cu = atoi(pc);
+  if (const char *sv = getenv("TFX_STAGGER")) h->stagger = atoi(sv) != 0;
   int dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) == hipSuccess) h->device = dev;
@@ -284,7 +245,6 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
 
   const int cars = d.C - 2;
   h->wpr = cars <= 64 ? 1 : (cars <= 128 ? 2 : 4);
-  h->grid_move = 0;  // sized at the first launch from the kernel's occupancy
 
   // tables
   const size_t R = (size_t)d.R;
@@ -426,10 +386,10 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
 int tfx_destroy(tfx_handle h) {
   if (!h) return TFX_OK;
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-  if (h->ag_exec) (void)hipGraphExecDestroy(h->ag_exec);
-  if (h->ag_graph) (void)hipGraphDestroy(h->ag_graph);
-  if (h->st_exec) (void)hipGraphExecDestroy(h->st_exec);
-  if (h->st_graph) (void)hipGraphDestroy(h->st_graph);
+  for (CapturedSeq &c : h->captured) {
+    if (c.exec) (void)hipGraphExecDestroy(c.exec);
+    if (c.graph) (void)hipGraphDestroy(c.graph);
+  }
   if (h->ag_stream) (void)hipStreamDestroy(h->ag_stream);
   if (h->split_stream) {
     (void)hipStreamSynchronize(h->split_stream);
@@ -758,13 +718,18 @@ int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
     }
     return TFX_OK;
   }
+  if (int rc = size_grids(h, false, n_ticks)) return rc;
   // Launch-bound handles (a few thousand tiles: cfg4 x 16, a 16x16 grid x 256 envs) replay the call's launches as a HIP
   // graph, like the fused agent step does: at cfg4 x 16 the kernels of a tick add up to 59 us of its 65.6
   // (profiles/r04_cfg4_closed_loop_trace.txt).  Not while kernels are timed, not for calls that split over two streams.
   const Dev &d = h->d;
   if (h->use_graph && !h->prof && n_ticks >= 4 && d.layout == 1 && (long)d.E * d.G <= (long)h->n_cu * 24 &&
-      !split_usable(h, n_ticks))
-    return step_graph(h, n_ticks, st);
+      !split_usable(h, n_ticks)) {
+    // captured once per distinct sequence (graph_key), replayed afterwards
+    char key[1280];
+    graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
+    return run_captured(h, h->captured[SEQ_STEP], key, st, [&](hipStream_t cs) { return step_body(h, n_ticks, cs); });
+  }
   return step_body(h, n_ticks, st);
 }
 
@@ -787,13 +752,15 @@ extern "C" {
 
 int tfx_move_cars(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
+  if (int rc = size_grids(h, false, 1)) return rc;
   if (int rc = launch_greedy(h, (hipStream_t)stream)) return rc;
   if (int rc = launch_inputs(h, (hipStream_t)stream)) return rc;
-  return (pairs_usable(h) && !single_tick_ts(h)) ? launch_move_tt<false>(h, 0, (hipStream_t)stream) : launch_move(h, 0, (hipStream_t)stream);
+  return (pairs_usable(h) && !single_tick_ts(h)) ? launch_move_tt(h, false, false, 0, (hipStream_t)stream) : launch_move(h, 0, (hipStream_t)stream);
 }
 
 int tfx_advance_finished_cars(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
+  if (int rc = size_grids(h, false, 1)) return rc;
   return launch_advance(h, 0, (hipStream_t)stream);
 }
 

@@ -1,6 +1,18 @@
-// tfx_launch.hpp - which kernel moves the cars of a handle, with what grid, and the launch helpers of the per-tick
-// kernels (host side; included by tfx_hip.hip).
+// tfx_launch.hpp - which kernel runs for a handle, with what grid, and the launch helpers of the per-tick kernels
+// (host side; included by tfx_hip.hip).  Three steps, each in one place:
+//   pick    one pick_* function per kernel family turns handle state into an instantiation: the function, the name
+//           tfx_step_kernel reports, the workgroup size and the dynamic LDS (Pick).  Nothing else names an instantiation
+//           of those families, so what was measured for a grid is what is launched with it.
+//   size    size_grids fills the grids of the handle, once each, at the ENTRY of every API call that launches the
+//           per-tick kernels - ahead of any stream capture, fork or SeqGuard.  Occupancy queries and function attributes
+//           must not run inside a capture, and a grid is that of the whole env range whichever half of a split call
+//           uses it first.
+//   launch  the launch_* functions launch what the pick names with the grid the handle holds, and note the mover in
+//           step_kernel; they size nothing.
+// (k_res is sized when the buffers are bound: res_configure.)
 #pragma once
+#include <map>
+
 #include "tfx_handle.hpp"
 #include "tfx_move_generic.hpp"
 #include "tfx_move_dma.hpp"
@@ -14,66 +26,42 @@
 
 namespace {
 
+// An instantiation of a per-tick kernel as its picker chose it
+template <class Fn>
+struct Pick {
+  Fn fn;
+  const char *name = "";  // the movers': what tfx_step_kernel reports
+  int block = 256;
+  size_t lds = 0;
+  long items = 0;  // the one-tick movers': work items a workgroup takes per pass (move_grid); 0 = a tile (k_move_ts)
+};
+using TickFn = void (*)(Dev, int);        // (d, tidx)
+using TickFn3 = void (*)(Dev, int, int);  // k_move_tt: (d, tidx, only_risky); k_tail: (d, tidx, flags)
+
 // Grid of the move kernel: every block resident at once (occupancy query), a multiple of 8 so the
 // XCD-contiguous chunking applies, never more blocks than there is work.
-template <typename K>
-int move_grid(tfx_handle h, K kernel, long work_items_per_block, size_t dyn_lds = 0, int cap = 5) {
+int move_grid(tfx_handle h, const Pick<TickFn> &p) {
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, dyn_lds) != hipSuccess || per_cu < 1)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.fn, p.block, p.lds) != hipSuccess || per_cu < 1)
     per_cu = 4;
   // more resident waves than ~5 blocks per CU only adds concurrent DRAM streams: measured at cfg2
-  // 3/4/5/6/7/8 blocks per CU -> 0.763/0.721/0.711/0.720/0.804/0.761 ms (k_move_t; k_move_tt takes 6, see there)
-  if (per_cu > cap) per_cu = cap;
-  if (const char *pc = getenv("TFX_MOVE_BLOCKS_PER_CU")) per_cu = atoi(pc) > 0 ? atoi(pc) : per_cu;
+  // 3/4/5/6/7/8 blocks per CU -> 0.763/0.721/0.711/0.720/0.804/0.761 ms (k_move_t; k_move_tt takes 6, see size_grids)
+  if (per_cu > 5) per_cu = 5;
+  if (h->move_blocks_per_cu > 0) per_cu = h->move_blocks_per_cu;
   const long total = h->d.layout == 1 ? (long)h->d.E * h->d.G * 64 : (long)h->d.E * h->d.R;
-  const long need = (total + work_items_per_block - 1) / work_items_per_block;
+  const long need = (total + p.items - 1) / p.items;
   long g = (long)h->n_cu * per_cu;
   if (g > need) g = need;
   if (g >= 8) g -= g % 8;
   return (int)(g < 1 ? 1 : g);
 }
 
-// k_move_dma<CC, S, NBUF, UNR, LEADER_LDS>: size the grid on first use, then launch
-template <int CC, int S, int NBUF, int UNR, bool LDSL, int LIVE = 0, int NP = 1>
-int launch_dma(tfx_handle h, int tidx, hipStream_t st) {
-  auto kern = k_move_dma<CC, S, NBUF, UNR, LDSL, LIVE, NP>;
-  h->step_kernel = "k_move_dma";
-  if (h->grid_move == 0) {
-    h->move_lds = (size_t)4 * NBUF * S * h->d.C * sizeof(float2);
-    if (h->move_lds > 64 * 1024)
-      HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->move_lds));
-    h->grid_move = move_grid(h, kern, 256, h->move_lds);
-  }
-  if (h->size_only) return TFX_OK;
-  TFX_INJECT(h);
-  hipLaunchKernelGGL(kern, dim3(h->grid_move), dim3(256), h->move_lds, st, h->d, tidx);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
-}
-
-template <int WPR>
-int launch_generic(tfx_handle h, int tidx, hipStream_t st) {
-  h->step_kernel = "k_move";
-  if (h->grid_move == 0) h->grid_move = move_grid(h, k_move<WPR>, 256 / (64 * WPR));
-  if (h->size_only) return TFX_OK;
-  TFX_INJECT(h);
-  hipLaunchKernelGGL(k_move<WPR>, dim3(h->grid_move), dim3(256), 0, st, h->d, tidx);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
-}
-
 // Transposed layout.  TFX_MOVE_VARIANT: 0 = automatic | 90 / 91 force / forbid the four-waves-per-tile kernel
 // (tests run k_move_t at sizes the heuristics would give to k_move_ts)
-int launch_move_t(tfx_handle h, int tidx, hipStream_t st) {
+Pick<TickFn> pick_move_t(const tfx_handle_s *h) {
   const int pvar = h->move_variant;
-  auto go = [&](auto kern) {
-    if (h->grid_move == 0) h->grid_move = move_grid(h, kern, 256);
-    if (h->size_only) return (int)TFX_OK;
-    TFX_INJECT(h);
-    hipLaunchKernelGGL(kern, dim3(h->grid_move), dim3(256), 0, st, h->d, tidx);
-    HIPCHK(hipGetLastError());
-    return (int)TFX_OK;
-  };
+  auto t = [](TickFn fn) { return Pick<TickFn>{fn, "k_move_t", 256, 0, 256}; };
+  auto ts = [](TickFn fn, int threads = 256) { return Pick<TickFn>{fn, "k_move_ts", threads, 0, 0}; };
   // Launches too small to fill the chip with one wavefront per tile: four wavefronts per tile
   // (TFX_MOVE_VARIANT 90 forces it, 91 forbids it)
   const long tiles = (long)h->d.E * h->d.G;
@@ -81,74 +69,65 @@ int launch_move_t(tfx_handle h, int tidx, hipStream_t st) {
   // (260) 0.075 -> 0.028, cfg1 x 256 (320) 0.023 -> 0.016, cfg4 x 4 (1040 tiles of 128 rows) 0.102 ->
   // 0.083; no gain at cfg2 x 64 (1088) and a loss at cfg1 x 1024 (1280): there the redundant road
   // prologues outweigh the shorter walks
-  if (h->het) {  // heterogeneous cars: the one kernel that reads a car's parameters from its table row
-    h->step_kernel = "k_move_t";
-    return go(k_move_t<4, 3, true, true>);
-  }
+  if (h->het) return t(k_move_t<4, 3, true, true>);  // heterogeneous cars: the one kernel that reads a car's parameters from its table row
   const long split_below = (h->d.C - 2 > 64) ? (long)h->n_cu * 9 / 2 : (long)h->n_cu * 2;
   if (pvar == 90 || (tiles <= split_below && pvar == 0)) {
-    auto gs = [&](auto kern, int threads = 256) {
-      if (h->grid_move == 0) h->grid_move = (int)(tiles < (long)h->n_cu * 8 ? tiles : (long)h->n_cu * 8);
-      if (h->size_only) return (int)TFX_OK;
-    TFX_INJECT(h);
-      hipLaunchKernelGGL(kern, dim3(h->grid_move), dim3(threads), 0, st, h->d, tidx);
-      HIPCHK(hipGetLastError());
-      return (int)TFX_OK;
-    };
     const int cap = h->d.C - 2;
     if (h->d.w) {
-      if (cap <= 32) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<8, true>); }
-      if (cap <= 64) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<16, true>); }
-      if (cap <= 128) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<32, true>); }
-      { h->step_kernel = "k_move_ts"; return gs(k_move_ts<64, true>); }
+      if (cap <= 32) return ts(k_move_ts<8, true>);
+      if (cap <= 64) return ts(k_move_ts<16, true>);
+      if (cap <= 128) return ts(k_move_ts<32, true>);
+      return ts(k_move_ts<64, true>);
     }
-    if (cap <= 32) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<8>); }
-    if (cap <= 64) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<16>); }
+    if (cap <= 32) return ts(k_move_ts<8>);
+    if (cap <= 64) return ts(k_move_ts<16>);
     // long roads on a launch of at most ~two tiles per CU: sixteen segments of 8 cars instead of four of 32
     // (cfg4 x 1 env closed loop, eight of 16: 38.4 -> 28.6 us per tick)
     // (sixteen of 8: 29.6 -> 28.8 us per tick at one env, 39.2 -> 37.7 at two - what is left is the launches' own latency)
-    if (cap <= 128 && cap > 64 && tiles <= (long)h->n_cu * 2) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<8, false, 16>, 1024); }
-    if (cap <= 128) { h->step_kernel = "k_move_ts"; return gs(k_move_ts<32>); }
-    { h->step_kernel = "k_move_ts"; return gs(k_move_ts<64>); }
+    if (cap <= 128 && cap > 64 && tiles <= (long)h->n_cu * 2) return ts(k_move_ts<8, false, 16>, 1024);
+    if (cap <= 128) return ts(k_move_ts<32>);
+    return ts(k_move_ts<64>);
   }
-  if (h->d.w) { h->step_kernel = "k_move_t"; return go(k_move_t<4, 3, true>); }  // validate mode: the spawn-tick plane travels along
+  if (h->d.w) return t(k_move_t<4, 3, true>);  // validate mode: the spawn-tick plane travels along
   // Cars that fit the 256 MiB Infinity Cache (+ L2) are found there again next tick: default caching
   // and 8 rows in flight.  Measured k_move_t<8> vs <4, nt> per launch: cfg2 x 128 envs (143 MB of cars)
   // 0.0365 vs 0.0392 ms, x 256 0.048 vs 0.054, x 384 0.068 vs 0.080, x 512 (286 MB) 0.086 vs 0.093,
   // cfg4 x 16 (272 MB) 0.096 vs 0.103, x 24 (409 MB) 0.134 vs 0.150; at cfg2 x 1024 (573 MB) it is the
   // other way round: 0.199 vs 0.173.  (12 or 16 rows in flight, or 8 resident blocks per CU: no better.)
-  if (pvar == 0 && h->n_tpairs * sizeof(float2) <= (size_t)448 << 20) { h->step_kernel = "k_move_t"; return go(k_move_t<8>); }
+  if (pvar == 0 && h->n_tpairs * sizeof(float2) <= (size_t)448 << 20) return t(k_move_t<8>);
   // beyond that every row is read once and written once per tick: non-temporal loads AND stores (0.82 -> 0.70 ms
   // at cfg2, and the following k_advance no longer waits for dirty lines: 0.057 -> 0.032 ms)
-  { h->step_kernel = "k_move_t"; return go(k_move_t<4, 3>); }
+  return t(k_move_t<4, 3>);
 }
 
-// Ring layout.  TFX_MOVE_VARIANT: 0 = automatic | 1 generic k_move<1> | 26 k_move_dma with the capacity read at run time
-int launch_move(tfx_handle h, int tidx, hipStream_t st) {
-  if (h->d.layout == 1) return launch_move_t(h, tidx, st);
+// k_move_dma<CC, S, NBUF, UNR, LEADER_LDS>: NBUF buffers of S rows of four planes in LDS
+template <int CC, int S, int NBUF, int UNR, bool LDSL, int LIVE = 0, int NP = 1>
+Pick<TickFn> pick_dma(const tfx_handle_s *h) {
+  return {k_move_dma<CC, S, NBUF, UNR, LDSL, LIVE, NP>, "k_move_dma", 256, (size_t)4 * NBUF * S * h->d.C * sizeof(float2), 256};
+}
+
+template <int WPR>
+Pick<TickFn> pick_generic() {
+  return {k_move<WPR>, "k_move", 256, 0, 256 / (64 * WPR)};
+}
+
+// The one-tick mover.  Ring layout: TFX_MOVE_VARIANT: 0 = automatic | 1 generic k_move<1> | 26 k_move_dma with the
+// capacity read at run time
+Pick<TickFn> pick_move(const tfx_handle_s *h) {
+  if (h->d.layout == 1) return pick_move_t(h);
   const int C = h->d.C;
   const int v = h->move_variant;
   // cfg4: 128-car roads take two passes of a wavefront through the tiled kernel
-  if (C == 130 && v != 1 && (long)h->d.E * h->d.R >= 64L * h->n_cu)
-    return launch_dma<130, 8, 2, 2, false, 2, 2>(h, tidx, st);
-  if (h->wpr == 2) return launch_generic<2>(h, tidx, st);
-  if (h->wpr == 4) return launch_generic<4>(h, tidx, st);
-  if ((C & 1) || v == 1) return launch_generic<1>(h, tidx, st);  // odd capacity: records not 16-B multiples
+  if (C == 130 && v != 1 && (long)h->d.E * h->d.R >= 64L * h->n_cu) return pick_dma<130, 8, 2, 2, false, 2, 2>(h);
+  if (h->wpr == 2) return pick_generic<2>();
+  if (h->wpr == 4) return pick_generic<4>();
+  if ((C & 1) || v == 1) return pick_generic<1>();  // odd capacity: records not 16-B multiples
   // fewer roads than one 64-road tile per CU: the tiled kernel would leave most CUs idle and walk
   // its tile serially; one wavefront per road finishes sooner
-  if (v == 0 && (long)h->d.E * h->d.R < 64L * h->n_cu) return launch_generic<1>(h, tidx, st);
-  if (C == 34) return launch_dma<34, 8, 2, 4, false, 2>(h, tidx, st);   // cfg1
-  if (C != 66 || v == 26) return launch_dma<0, 8, 1, 8, false>(h, tidx, st);  // capacity read at run time
-  return launch_dma<66, 8, 2, 4, false, 2>(h, tidx, st);  // cfg2: best of the tuning runs
-}
-
-// sizes the move kernel's grid without launching (the occupancy queries must not run inside a
-// stream capture)
-int launch_move_probe(tfx_handle h) {
-  h->size_only = true;
-  const int rc = launch_move(h, 0, nullptr);
-  h->size_only = false;
-  return rc;
+  if (v == 0 && (long)h->d.E * h->d.R < 64L * h->n_cu) return pick_generic<1>();
+  if (C == 34) return pick_dma<34, 8, 2, 4, false, 2>(h);   // cfg1
+  if (C != 66 || v == 26) return pick_dma<0, 8, 1, 8, false>(h);  // capacity read at run time
+  return pick_dma<66, 8, 2, 4, false, 2>(h);  // cfg2: best of the tuning runs
 }
 
 int grid_for(long items, int n_cu) {
@@ -349,36 +328,11 @@ int launch_res(tfx_handle h, int n_ticks, hipStream_t st, int tail = 0, int remi
   return TFX_OK;
 }
 
-int launch_advance(tfx_handle h, int tidx, hipStream_t st) {
-  const Dev &d = h->d;
-  if (h->grid_adv == 0) {
-    // no more blocks than are resident at once (k_advance<true> holds 5 per CU): with 8 per CU launched the
-    // last three of every CU start when the first five have finished their whole grid-stride loop
-    const long items = (long)d.E * (d.I + d.R - d.r);
-    int per_cu = 0;
-    const hipError_t qe = d.layout == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_advance<true>, 256, 0)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_advance<false>, 256, 0);
-    if (qe != hipSuccess || per_cu < 1) per_cu = 4;
-    if (per_cu > 8) per_cu = 8;
-    long g = (items + 255) / 256;
-    if (g > (long)h->n_cu * per_cu) g = (long)h->n_cu * per_cu;
-    h->grid_adv = (int)(g < 1 ? 1 : g);
-  }
-  if (h->size_only) return TFX_OK;
-  TFX_INJECT(h);
-  const bool g = h->greedy;
-  if (h->het) {
-    if (g) hipLaunchKernelGGL((k_advance<true, true, true>), dim3(h->grid_adv), dim3(256), 0, st, d, tidx);
-    else hipLaunchKernelGGL((k_advance<true, true>), dim3(h->grid_adv), dim3(256), 0, st, d, tidx);
-  } else if (d.layout == 1) {
-    if (g) hipLaunchKernelGGL((k_advance<true, false, true>), dim3(h->grid_adv), dim3(256), 0, st, d, tidx);
-    else hipLaunchKernelGGL(k_advance<true>, dim3(h->grid_adv), dim3(256), 0, st, d, tidx);
-  } else {
-    if (g) hipLaunchKernelGGL((k_advance<false, false, true>), dim3(h->grid_adv), dim3(256), 0, st, d, tidx);
-    else hipLaunchKernelGGL(k_advance<false>, dim3(h->grid_adv), dim3(256), 0, st, d, tidx);
-  }
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+// k_advance<TL, HET, GREEDY> (heterogeneous cars live in the transposed layout)
+Pick<TickFn> pick_advance(bool transposed, bool het, bool greedy) {
+  if (het) return {greedy ? k_advance<true, true, true> : k_advance<true, true>};
+  if (transposed) return {greedy ? k_advance<true, false, true> : k_advance<true>};
+  return {greedy ? k_advance<false, false, true> : k_advance<false>};
 }
 
 // Two ticks per pass over the cars (tfx_move_tt.hpp): for calls of two ticks or more on the transposed
@@ -412,17 +366,11 @@ bool single_tick_ts(const tfx_handle_s *h) {
   return !h->het && h->move_variant == 0 && h->d.layout == 1 && tiles <= split_below;
 }
 
-int edge_grid(tfx_handle h) {
-  if (h->grid_edge == 0) {  // every block resident at once: a second, nearly empty round would double the time
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_edge<false, false>), 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-    if (per_cu > 6) per_cu = 6;  // measured at cfg2, 4 / 5 / 6 / 7 blocks per CU: 0.112 / 0.102 / 0.097 / 0.118 ms
-    const long tiles = (long)h->d.E * h->d.G;
-    long g = (long)h->n_cu * per_cu;
-    if (g > (tiles + 3) / 4) g = (tiles + 3) / 4;
-    h->grid_edge = (int)(g < 1 ? 1 : g);
-  }
-  return h->grid_edge;
+// k_edge<AGENT, W, HET> (heterogeneous cars carry the side-word plane)
+Pick<TickFn> pick_edge(bool agent, bool w, bool het) {
+  if (het) return {agent ? k_edge<true, true, true> : k_edge<false, true, true>};
+  if (w) return {agent ? k_edge<true, true> : k_edge<false, true>};
+  return {agent ? k_edge<true, false> : k_edge<false, false>};
 }
 
 // Wavefronts per tile of a two-tick pass (0: one, k_move_tt).  Measured (us per tick; S = 0 / 2 / 4 / 8):
@@ -444,96 +392,38 @@ int tt_segments(const tfx_handle_s *h) {
   return 0;
 }
 
-// AGENT: inside an agent step; only_risky: the second tick of the envs k_risk sorted out of a pair
-// crec: k_tail follows this (two-tick) pass - the road records go out in their 8-byte form (Dev::crec)
-// rsw: ... and a k_tail of the same call came before it - the ring indices come from its road state words (Dev::rsw)
-template <bool TWO, bool AGENT = false>
-int launch_move_tt(tfx_handle h, int tidx, hipStream_t st, int only_risky = 0, bool crec = false, bool rsw = false) {
-  // Grid: 16 workgroups per CU, 6 of them resident at once: later rounds of workgroups even out the end of the launch.
-  // Measured at cfg2, round 4 (k_tail with its lighter records), split call, same box, workgroups per CU -> ms per tick /
-  // ms per pass on the chip: 6 -> 0.396 / 0.739; 8 -> 0.404 / 0.755; 10 -> 0.387-0.392 / 0.702-0.706; 12 -> 0.382 / 0.713;
-  // 14 -> 0.379 / 0.696; 16 -> 0.377-0.380 / 0.695-0.698; 18 -> 0.387 / 0.688; 20 -> 0.400 / 0.695; 24 -> 0.401 / 0.681;
-  // one workgroup per four tiles (34 per CU) -> 0.412 / 0.698 (tools/sweep_blocks.sh; another box 10 / 15 / 16 / 17:
-  // 0.391-0.393 / 0.386 / 0.388-0.389 / 0.388-0.389, agent decision 4.52-4.54 / 4.45 / 4.43-4.46 / 4.39-4.44 ms).
-  // Round 3, with the heavier k_tail behind the pass, had its optimum at 10.  More rounds than ~16 per CU cost the split
-  // call more than they give the launch.  (Grids of a whole number of workgroups per CU: an "exactly balanced" 2902
-  // instead of 3072 workgroups took 0.756.)
-  int &resident = h->grid_tt[(TWO ? 1 : 0) + (AGENT ? 2 : 0)];
-  if (resident == 0) {
-    int per_cu = 0;
-    const auto occ = h->d.het ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_move_tt<TWO, AGENT, true, true>, 256, 0)
-                     : h->d.w ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_move_tt<TWO, AGENT, true>, 256, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_move_tt<TWO, AGENT, false>, 256, 0);
-    if (occ != hipSuccess || per_cu < 1) per_cu = 4;
-    if (per_cu > 6) per_cu = 6;
-    resident = h->n_cu * per_cu;
+// k_move_tt<TWO, AGENT, W, HET, CREC, RSW>.  two: a two-tick pass, otherwise the one-tick form; agent: inside an agent
+// step.  crec: k_tail follows this (two-tick) pass - the road records go out in their 8-byte form (Dev::crec); rsw: ...
+// and a k_tail of the same call came before it - the ring indices come from its road state words (Dev::rsw; plain cars
+// in plain tfx_step calls)
+template <bool TWO, bool AGENT, bool CREC = false, bool RSW = false>
+Pick<TickFn3> tt_form(const Dev &d) {
+  if constexpr (!RSW) {
+    if (d.het) return {k_move_tt<TWO, AGENT, true, true, CREC>, "k_move_tt"};
   }
-  h->step_kernel = "k_move_tt";
-  if (h->size_only) return TFX_OK;
-  TFX_INJECT(h);
-  long grid = (long)resident * 16 / 6;
-  if (const char *pc = getenv("TFX_MOVE_BLOCKS_PER_CU")) grid = atoi(pc) > 0 ? (long)atoi(pc) * h->n_cu : grid;
-  const long need = ((long)h->d.E * h->d.G + 3) / 4;
-  if (grid > need) grid = need;
-  if (grid >= 8) grid -= grid % 8;
-  if (grid < 1) grid = 1;
-  static const bool want_stagger = !(getenv("TFX_STAGGER") && atoi(getenv("TFX_STAGGER")) == 0);
-  const bool stagger = want_stagger && TWO && h->split_first && h->split_half >= 0;
-  if (stagger && h->split_half == 1) HIPCHK(hipStreamWaitEvent(st, h->split_stagger, 0));
-  // Launches that leave most wave slots empty with one wavefront per tile: the tiles' walks split over 2, 4 or 8
-  // wavefronts (tfx_move_tts.hpp, tt_segments; plain cars).  TFX_TT_SEG=0 never, 2 whenever the form
-  // exists; TFX_TT_SEGS = 2 / 4 / 8 forces the number.
-  if (TWO && !only_risky && !h->d.het && h->tt_seg &&
-      (h->tt_seg == 2 || (h->split_half < 0 && tt_segments(h) > 0))) {
-    const long tiles_all = (long)h->d.E * h->d.G;
-    int S = tt_segments(h);
-    if (S == 0) S = 2;  // (forced: TFX_TT_SEG=2)
-    if (h->tt_segs == 2 || h->tt_segs == 4 || h->tt_segs == 8) S = h->tt_segs;
-    const long groups = S == 2 ? (tiles_all + 1) / 2 : tiles_all;
-    long gs = (long)h->n_cu * 16;  // (workgroups stride over the tiles)
-    if (gs > groups) gs = groups;
-    const dim3 g2((unsigned)gs), b2(S == 2 ? 256 : 64 * S);
-#define TFX_TTS_LAUNCH(SEGS)                                                                                   \
-    do {                                                                                                       \
-      if (h->d.w) {                                                                                                      \
-        if (AGENT && crec) hipLaunchKernelGGL((k_move_tts<AGENT, true, false, SEGS, true>), g2, b2, 0, st, h->d, tidx);   \
-        else if (AGENT) hipLaunchKernelGGL((k_move_tts<AGENT, false, false, SEGS, true>), g2, b2, 0, st, h->d, tidx);     \
-        else if (crec && rsw) hipLaunchKernelGGL((k_move_tts<false, true, true, SEGS, true>), g2, b2, 0, st, h->d, tidx); \
-        else if (crec) hipLaunchKernelGGL((k_move_tts<false, true, false, SEGS, true>), g2, b2, 0, st, h->d, tidx);       \
-        else hipLaunchKernelGGL((k_move_tts<false, false, false, SEGS, true>), g2, b2, 0, st, h->d, tidx);                \
-      } else if (AGENT && crec) hipLaunchKernelGGL((k_move_tts<AGENT, true, false, SEGS>), g2, b2, 0, st, h->d, tidx);    \
-      else if (AGENT) hipLaunchKernelGGL((k_move_tts<AGENT, false, false, SEGS>), g2, b2, 0, st, h->d, tidx);             \
-      else if (crec && rsw) hipLaunchKernelGGL((k_move_tts<false, true, true, SEGS>), g2, b2, 0, st, h->d, tidx);         \
-      else if (crec) hipLaunchKernelGGL((k_move_tts<false, true, false, SEGS>), g2, b2, 0, st, h->d, tidx);               \
-      else hipLaunchKernelGGL((k_move_tts<false, false, false, SEGS>), g2, b2, 0, st, h->d, tidx);                        \
-    } while (0)
-    if (S == 8) TFX_TTS_LAUNCH(8);  // (sixteen: cfg4 x 1 env 25.1 against 24.6 us per tick, prefilled 21.4 against 18.5)
-    else if (S == 4) TFX_TTS_LAUNCH(4);
-    else TFX_TTS_LAUNCH(2);
-#undef TFX_TTS_LAUNCH
-    HIPCHK(hipGetLastError());
-    h->step_kernel = "k_move_tts";
-    if (stagger && h->split_half == 0) HIPCHK(hipEventRecord(h->split_stagger, st));
-    if (stagger) h->split_first = false;
-    return TFX_OK;
-  }
-  const dim3 g((unsigned)grid), b(256);
-  if (TWO && crec && rsw && !AGENT && !h->d.het) {
-    constexpr bool CR = TWO && !AGENT;
-    if (h->d.w) hipLaunchKernelGGL((k_move_tt<CR, false, true, false, CR, CR>), g, b, 0, st, h->d, tidx, only_risky);
-    else hipLaunchKernelGGL((k_move_tt<CR, false, false, false, CR, CR>), g, b, 0, st, h->d, tidx, only_risky);
-  } else if (TWO && crec) {  // (k_tail follows)
-    constexpr bool CR = TWO;
-    if (h->d.het) hipLaunchKernelGGL((k_move_tt<CR, AGENT, true, true, CR>), g, b, 0, st, h->d, tidx, only_risky);
-    else if (h->d.w) hipLaunchKernelGGL((k_move_tt<CR, AGENT, true, false, CR>), g, b, 0, st, h->d, tidx, only_risky);
-    else hipLaunchKernelGGL((k_move_tt<CR, AGENT, false, false, CR>), g, b, 0, st, h->d, tidx, only_risky);
-  } else if (h->d.het) hipLaunchKernelGGL((k_move_tt<TWO, AGENT, true, true>), g, b, 0, st, h->d, tidx, only_risky);
-  else if (h->d.w) hipLaunchKernelGGL((k_move_tt<TWO, AGENT, true>), g, b, 0, st, h->d, tidx, only_risky);
-  else hipLaunchKernelGGL((k_move_tt<TWO, AGENT, false>), g, b, 0, st, h->d, tidx, only_risky);
-  HIPCHK(hipGetLastError());
-  if (stagger && h->split_half == 0) HIPCHK(hipEventRecord(h->split_stagger, st));
-  if (stagger) h->split_first = false;
-  return TFX_OK;
+  if (d.w) return {k_move_tt<TWO, AGENT, true, false, CREC, RSW>, "k_move_tt"};
+  return {k_move_tt<TWO, AGENT, false, false, CREC, RSW>, "k_move_tt"};
+}
+Pick<TickFn3> pick_tt(const Dev &d, bool two, bool agent, bool crec = false, bool rsw = false) {
+  if (two && crec && rsw && !agent && !d.het) return tt_form<true, false, true, true>(d);
+  if (two && crec) return agent ? tt_form<true, true, true>(d) : tt_form<true, false, true>(d);
+  if (two) return agent ? tt_form<true, true>(d) : tt_form<true, false>(d);
+  return agent ? tt_form<false, true>(d) : tt_form<false, false>(d);
+}
+
+// k_move_tts<AGENT, CREC, RSW, S, W>: the two-tick pass of plain cars with S = 2 / 4 / 8 wavefronts per tile
+template <int S, bool W>
+Pick<TickFn> tts_form(bool agent, bool crec, bool rsw) {
+  TickFn fn = k_move_tts<false, false, false, S, W>;
+  if (agent) fn = crec ? k_move_tts<true, true, false, S, W> : k_move_tts<true, false, false, S, W>;
+  else if (crec) fn = rsw ? k_move_tts<false, true, true, S, W> : k_move_tts<false, true, false, S, W>;
+  return {fn, "k_move_tts", S == 2 ? 256 : 64 * S};
+}
+Pick<TickFn> pick_tts(int S, bool w, bool agent, bool crec, bool rsw) {
+  // (sixteen: cfg4 x 1 env 25.1 against 24.6 us per tick, prefilled 21.4 against 18.5)
+  if (S == 8) return w ? tts_form<8, true>(agent, crec, rsw) : tts_form<8, false>(agent, crec, rsw);
+  if (S == 4) return w ? tts_form<4, true>(agent, crec, rsw) : tts_form<4, false>(agent, crec, rsw);
+  return w ? tts_form<2, true>(agent, crec, rsw) : tts_form<2, false>(agent, crec, rsw);
 }
 
 // The envs [lo, lo + n) of a handle as a Dev of their own: every per-env array starts at env lo, the global env
@@ -587,12 +477,13 @@ Dev sub_dev(const tfx_handle_s *h, int lo, int n, int *clock) {
 
 // k_tail (tfx_tail.hpp) replaces k_advance(t) k_edge(t+1) k_advance(t+1) behind a two-tick pass: one workgroup per
 // env, the env's ring words staged in LDS.  Not when the arrivals of t+1 are produced by a launch between the two ticks
-// (the Poisson stream tick by tick: agent steps; tfx_step generates them up front), not below one env per CU (a handful
+// (the Poisson stream tick by tick: agent steps; tfx_step generates them up front - `upfront` asks ahead of that, at
+// the call's entry), not below one env per CU (a handful
 // of big envs - cfg4 - has too few workgroups to offer), and not when an env's words do not fit a workgroup's LDS.
 // (The greedy controller decides inside the advance.)
 constexpr size_t TAIL_LDS_MAX = (size_t)160 * 1024;
-bool tail_usable(tfx_handle h) {
-  if (!h->tail || (h->poisson && h->d.spawn_stride == 0) || h->d.layout != 1) return false;
+bool tail_usable(tfx_handle h, bool upfront = false) {
+  if (!h->tail || (h->poisson && h->d.spawn_stride == 0 && !upfront) || h->d.layout != 1) return false;
   if (tail_lds_bytes(h->d.R, h->d.I, h->het) > TAIL_LDS_MAX) return false;
   // (the halves of a split call - chosen for the whole range, split_usable - keep k_tail whatever their own size)
   return h->tail == 2 || h->d.E >= h->n_cu || h->split_half >= 0;
@@ -611,79 +502,185 @@ bool split_usable(tfx_handle h, int n_ticks) {
   return h->d.E / 2 >= h->n_cu * 3 / 4 && (long)(h->d.E / 2) * h->d.G >= (long)h->n_cu * 4;
 }
 
-// Workgroup size (the kernel takes any multiple of 64).  Alone on the chip 256 lanes and as many workgroups as fit; as
-// one half of a split tfx_step call, next to the other half's pass, 128 lanes (they fit the gaps the pass leaves).
-// Round 4 sweep with the staged kernel, cfg2, ms per tick (64 / 128 / 192 / 256 lanes in the halves): 0.419 / 0.399 /
-// 0.406 / 0.414; workgroups per CU capped at 2 / 3 / as many as fit: 0.414 / 0.419 / 0.399.
-template <bool GREEDY, bool AGENT, bool W, bool HET>
-int launch_tail_as(tfx_handle h, int tidx, hipStream_t st, int flags) {
-  auto kern = k_tail<GREEDY, AGENT, W, HET>;
-  const size_t lds = tail_lds_bytes(h->d.R, h->d.I, HET);
-  // (asked of HIP it would fail - and leave its error behind for the next launch's hipGetLastError to find)
-  if (lds > TAIL_LDS_MAX) return fail(TFX_ESTATE, "an env's ring words (%zu bytes) do not fit a workgroup's LDS", lds);
-  // The attribute belongs to the FUNCTION, not to the handle: only ever raised (see res_try)
-  static size_t granted = 64 * 1024;
-  if (lds > granted) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    granted = lds;
+// k_tail<GREEDY, AGENT, W, HET>, with the env's ring words as its dynamic LDS
+template <bool GREEDY, bool AGENT>
+Pick<TickFn3> tail_form(const Dev &d, size_t lds) {
+  if (d.het) return {k_tail<GREEDY, AGENT, true, true>, "", 256, lds};
+  if (d.w) return {k_tail<GREEDY, AGENT, true, false>, "", 256, lds};
+  return {k_tail<GREEDY, AGENT, false, false>, "", 256, lds};
+}
+Pick<TickFn3> pick_tail(const tfx_handle_s *h, bool agent) {
+  const size_t lds = tail_lds_bytes(h->d.R, h->d.I, h->het);
+  if (h->greedy) return agent ? tail_form<true, true>(h->d, lds) : tail_form<true, false>(h->d, lds);
+  return agent ? tail_form<false, true>(h->d, lds) : tail_form<false, false>(h->d, lds);
+}
+
+// Every grid a call of n_ticks ticks can launch with and that is still 0, from the WHOLE env range (h->d as the API
+// entry finds it); agent: the call is an agent step.  The only place that asks HIP for a kernel's occupancy or raises
+// its dynamic-LDS limit - neither may happen inside a stream capture - apart from res_configure.
+// (A call that k_res serves launches none of these kernels and does not come here; tfx_move_cars and
+// tfx_advance_finished_cars run the per-tick kernels on every handle, one that fits k_res included.)
+// grid_tail / grid_tail_half belong to the handle, not to an instantiation: they come from the k_tail of the first call
+// that can launch one - an agent step's or a plain call's - and serve both from then on.
+int size_grids(tfx_handle h, bool agent, int n_ticks) {
+  const Dev &d = h->d;
+  auto per_cu_of = [](auto fn, int threads, size_t lds, int otherwise) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess || per_cu < 1) per_cu = otherwise;
+    return per_cu;
+  };
+  // The attribute belongs to the FUNCTION, not to the handle: handles with different LDS needs share it, so it is
+  // only ever raised (a later, smaller handle must not pull it below what an earlier one launches with; see res_try)
+  static std::map<const void *, size_t> granted;  // per instantiation, process-wide; 64 KB are there without asking
+  auto raise_lds = [](const void *fn, size_t lds) -> int {
+    size_t &have = granted.emplace(fn, (size_t)64 * 1024).first->second;
+    if (lds > have) {
+      HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      have = lds;
+    }
+    return TFX_OK;
+  };
+  const long tiles = (long)d.E * d.G;
+  if (h->grid_move == 0) {
+    const Pick<TickFn> p = pick_move(h);
+    if (int rc = raise_lds((const void *)p.fn, p.lds)) return rc;
+    // (k_move_ts: a workgroup per tile, up to 8 per CU striding over more)
+    h->grid_move = p.items ? move_grid(h, p) : (int)(tiles < (long)h->n_cu * 8 ? tiles : (long)h->n_cu * 8);
   }
+  if (h->grid_adv == 0) {
+    // no more blocks than are resident at once (k_advance<true> holds 5 per CU): with 8 per CU launched the
+    // last three of every CU start when the first five have finished their whole grid-stride loop
+    const long items = (long)d.E * (d.I + d.R - d.r);
+    int per_cu = per_cu_of(pick_advance(d.layout == 1, false, false).fn, 256, 0, 4);
+    if (per_cu > 8) per_cu = 8;
+    long g = (items + 255) / 256;
+    if (g > (long)h->n_cu * per_cu) g = (long)h->n_cu * per_cu;
+    h->grid_adv = (int)(g < 1 ? 1 : g);
+  }
+  if (!pairs_usable(h)) return TFX_OK;
+  // k_move_tt.  Grid: 16 workgroups per CU, 6 of them resident at once: later rounds of workgroups even out the end of the launch.
+  // Measured at cfg2, round 4 (k_tail with its lighter records), split call, same box, workgroups per CU -> ms per tick /
+  // ms per pass on the chip: 6 -> 0.396 / 0.739; 8 -> 0.404 / 0.755; 10 -> 0.387-0.392 / 0.702-0.706; 12 -> 0.382 / 0.713;
+  // 14 -> 0.379 / 0.696; 16 -> 0.377-0.380 / 0.695-0.698; 18 -> 0.387 / 0.688; 20 -> 0.400 / 0.695; 24 -> 0.401 / 0.681;
+  // one workgroup per four tiles (34 per CU) -> 0.412 / 0.698 (tools/sweep_blocks.sh; another box 10 / 15 / 16 / 17:
+  // 0.391-0.393 / 0.386 / 0.388-0.389 / 0.388-0.389, agent decision 4.52-4.54 / 4.45 / 4.43-4.46 / 4.39-4.44 ms).
+  // Round 3, with the heavier k_tail behind the pass, had its optimum at 10.  More rounds than ~16 per CU cost the split
+  // call more than they give the launch.  (Grids of a whole number of workgroups per CU: an "exactly balanced" 2902
+  // instead of 3072 workgroups took 0.756.)
+  // grid_tt holds the RESIDENT workgroups of the form without k_tail's records; tt_grid makes the launch's grid of it.
+  for (int two = 0; two < 2; ++two) {
+    int &resident = h->grid_tt[two + (agent ? 2 : 0)];
+    if (resident == 0) {
+      int per_cu = per_cu_of(pick_tt(d, two, agent).fn, 256, 0, 4);
+      if (per_cu > 6) per_cu = 6;
+      resident = h->n_cu * per_cu;
+    }
+  }
+  if (h->grid_edge == 0) {  // k_edge and k_risk.  Every block resident at once: a second, nearly empty round would double the time
+    int per_cu = per_cu_of(pick_edge(false, false, false).fn, 256, 0, 4);
+    if (per_cu > 6) per_cu = 6;  // measured at cfg2, 4 / 5 / 6 / 7 blocks per CU: 0.112 / 0.102 / 0.097 / 0.118 ms
+    long g = (long)h->n_cu * per_cu;
+    if (g > (tiles + 3) / 4) g = (tiles + 3) / 4;
+    h->grid_edge = (int)(g < 1 ? 1 : g);
+  }
+  // (tfx_step has generated its arrivals by the time its pairs are enqueued: step_body)
+  if (n_ticks < 2 || !tail_usable(h, !agent)) return TFX_OK;
+  // k_tail.  Workgroup size (the kernel takes any multiple of 64).  Alone on the chip 256 lanes and as many workgroups as fit; as
+  // one half of a split tfx_step call, next to the other half's pass, 128 lanes (they fit the gaps the pass leaves).
+  // Round 4 sweep with the staged kernel, cfg2, ms per tick (64 / 128 / 192 / 256 lanes in the halves): 0.419 / 0.399 /
+  // 0.406 / 0.414; workgroups per CU capped at 2 / 3 / as many as fit: 0.414 / 0.419 / 0.399.
+  const Pick<TickFn3> p = pick_tail(h, agent);
+  if (int rc = raise_lds((const void *)p.fn, p.lds)) return rc;
   if (h->grid_tail == 0) {
     for (int half = 0; half < 2; ++half) {
       const int threads = half ? 128 : 256;
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-      long g = (long)h->n_cu * per_cu;
-      if (g > h->d.E) g = h->d.E;
+      long g = (long)h->n_cu * per_cu_of(p.fn, threads, p.lds, 1);
+      if (g > d.E) g = d.E;
       (half ? h->grid_tail_half : h->grid_tail) = (int)(g < 1 ? 1 : g);
       (half ? h->tail_threads_half : h->tail_threads) = threads;
     }
   }
-  if (h->size_only) return TFX_OK;
+  return TFX_OK;
+}
+
+// One launch of a picked kernel on the envs h->d describes; counted by tfx_debug_fail_after
+template <class Fn, class... Args>
+int launch(tfx_handle h, const Pick<Fn> &p, long grid, hipStream_t st, Args... args) {
   TFX_INJECT(h);
-  // (inside agent steps the whole-size workgroups win in the halves as well: measured at cfg2, 128 / 192 / 256 lanes:
-  // plain calls 0.399 / 0.406 / 0.414 ms per tick, fused decisions 4.72 / 4.63 / 4.51 ms)
-  // (... and so do halves of fewer than two envs per CU: cfg2 x 512 envs 65.1 against 72.5 us per tick, x 1024 112.8 /
-  // 112.1, x 2048 204.9 / 196.1)
-  const bool halves = h->split_half >= 0 && !AGENT && h->d.E >= 2 * h->n_cu;
-  const dim3 g(halves ? h->grid_tail_half : h->grid_tail), b(halves ? h->tail_threads_half : h->tail_threads);
-  hipLaunchKernelGGL(kern, g, b, lds, st, h->d, tidx, flags);
+  const Fn kern = p.fn;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(p.block), p.lds, st, h->d, args...);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
 
-int launch_tail(tfx_handle h, int tidx, hipStream_t st, bool agent = false, int flags = TAIL_LAST) {
-  const int sel = (h->greedy ? 1 : 0) | (agent ? 2 : 0) | (h->d.w ? 4 : 0) | (h->d.het ? 8 : 0);
-  switch (sel) {
-    case 12: return launch_tail_as<false, false, true, true>(h, tidx, st, flags);
-    case 13: return launch_tail_as<true, false, true, true>(h, tidx, st, flags);
-    case 14: return launch_tail_as<false, true, true, true>(h, tidx, st, flags);
-    case 15: return launch_tail_as<true, true, true, true>(h, tidx, st, flags);
-    case 0: return launch_tail_as<false, false, false, false>(h, tidx, st, flags);
-    case 1: return launch_tail_as<true, false, false, false>(h, tidx, st, flags);
-    case 2: return launch_tail_as<false, true, false, false>(h, tidx, st, flags);
-    case 3: return launch_tail_as<true, true, false, false>(h, tidx, st, flags);
-    case 4: return launch_tail_as<false, false, true, false>(h, tidx, st, flags);
-    case 5: return launch_tail_as<true, false, true, false>(h, tidx, st, flags);
-    case 6: return launch_tail_as<false, true, true, false>(h, tidx, st, flags);
-    default: return launch_tail_as<true, true, true, false>(h, tidx, st, flags);
-  }
+int launch_move(tfx_handle h, int tidx, hipStream_t st) {
+  const Pick<TickFn> p = pick_move(h);
+  h->step_kernel = p.name;
+  return launch(h, p, h->grid_move, st, tidx);
 }
 
-template <bool AGENT>
-int launch_edge(tfx_handle h, int tidx, hipStream_t st) {
-  TFX_INJECT(h);
-  if (h->d.het) hipLaunchKernelGGL((k_edge<AGENT, true, true>), dim3(edge_grid(h)), dim3(256), 0, st, h->d, tidx);
-  else if (h->d.w) hipLaunchKernelGGL((k_edge<AGENT, true>), dim3(edge_grid(h)), dim3(256), 0, st, h->d, tidx);
-  else hipLaunchKernelGGL((k_edge<AGENT, false>), dim3(edge_grid(h)), dim3(256), 0, st, h->d, tidx);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+int launch_advance(tfx_handle h, int tidx, hipStream_t st) {
+  return launch(h, pick_advance(h->d.layout == 1, h->het, h->greedy), h->grid_adv, st, tidx);
+}
+
+int launch_edge(tfx_handle h, bool agent, int tidx, hipStream_t st) {
+  return launch(h, pick_edge(agent, h->d.w != nullptr, h->d.het), h->grid_edge, st, tidx);
 }
 
 int launch_risk(tfx_handle h, int tidx, hipStream_t st) {
-  TFX_INJECT(h);
-  hipLaunchKernelGGL(k_risk, dim3(edge_grid(h)), dim3(256), 0, st, h->d, tidx);
-  HIPCHK(hipGetLastError());
+  return launch(h, Pick<TickFn>{k_risk}, h->grid_edge, st, tidx);
+}
+
+// One pass over the cars of a handle that runs pairs: two ticks (two) or the one-tick form; only_risky: the second tick
+// of the envs k_risk sorted out of a pair; crec, rsw: see pick_tt
+int launch_move_tt(tfx_handle h, bool two, bool agent, int tidx, hipStream_t st, int only_risky = 0, bool crec = false,
+                   bool rsw = false) {
+  const Dev &d = h->d;
+  const long tiles = (long)d.E * d.G;
+  const bool stagger = h->stagger && two && h->split_first && h->split_half >= 0;
+  if (stagger && h->split_half == 1) HIPCHK(hipStreamWaitEvent(st, h->split_stagger, 0));
+  int rc;
+  // Launches that leave most wave slots empty with one wavefront per tile: the tiles' walks split over 2, 4 or 8
+  // wavefronts (tfx_move_tts.hpp, tt_segments; plain cars).  TFX_TT_SEG=0 never, 2 whenever the form
+  // exists; TFX_TT_SEGS = 2 / 4 / 8 forces the number.
+  if (two && !only_risky && !d.het && h->tt_seg && (h->tt_seg == 2 || (h->split_half < 0 && tt_segments(h) > 0))) {
+    int S = tt_segments(h);
+    if (S == 0) S = 2;  // (forced: TFX_TT_SEG=2)
+    if (h->tt_segs == 2 || h->tt_segs == 4 || h->tt_segs == 8) S = h->tt_segs;
+    const long groups = S == 2 ? (tiles + 1) / 2 : tiles;
+    long grid = (long)h->n_cu * 16;  // (workgroups stride over the tiles)
+    if (grid > groups) grid = groups;
+    const Pick<TickFn> p = pick_tts(S, d.w != nullptr, agent, crec, rsw);
+    h->step_kernel = p.name;
+    rc = launch(h, p, grid, st, tidx);
+  } else {
+    // 16 workgroups per CU for the 6 resident ones size_grids found (see there), never more than there is work
+    long grid = (long)h->grid_tt[(two ? 1 : 0) + (agent ? 2 : 0)] * 16 / 6;
+    if (h->move_blocks_per_cu > 0) grid = (long)h->move_blocks_per_cu * h->n_cu;
+    const long need = (tiles + 3) / 4;
+    if (grid > need) grid = need;
+    if (grid >= 8) grid -= grid % 8;
+    if (grid < 1) grid = 1;
+    const Pick<TickFn3> p = pick_tt(d, two, agent, crec, rsw);
+    h->step_kernel = p.name;
+    rc = launch(h, p, grid, st, tidx, only_risky);
+  }
+  if (rc != TFX_OK) return rc;
+  if (stagger && h->split_half == 0) HIPCHK(hipEventRecord(h->split_stagger, st));
+  if (stagger) h->split_first = false;
   return TFX_OK;
+}
+
+// The rest of a pair behind its two-tick pass (tail_usable).
+// (inside agent steps the whole-size workgroups win in the halves as well: measured at cfg2, 128 / 192 / 256 lanes:
+// plain calls 0.399 / 0.406 / 0.414 ms per tick, fused decisions 4.72 / 4.63 / 4.51 ms)
+// (... and so do halves of fewer than two envs per CU: cfg2 x 512 envs 65.1 against 72.5 us per tick, x 1024 112.8 /
+// 112.1, x 2048 204.9 / 196.1)
+int launch_tail(tfx_handle h, int tidx, hipStream_t st, bool agent = false, int flags = TAIL_LAST) {
+  Pick<TickFn3> p = pick_tail(h, agent);
+  const bool halves = h->split_half >= 0 && !agent && h->d.E >= 2 * h->n_cu;
+  p.block = halves ? h->tail_threads_half : h->tail_threads;
+  return launch(h, p, halves ? h->grid_tail_half : h->grid_tail, st, tidx, flags);
 }
 
 }  // namespace

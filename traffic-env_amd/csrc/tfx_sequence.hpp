@@ -1,5 +1,8 @@
 // tfx_sequence.hpp - the launch sequences of tfx_step and tfx_agent_step: pairs of ticks, the env range in two halves on
-// two streams, the agent step (host side; included by tfx_hip.hip).
+// two streams, the agent step (host side; included by tfx_hip.hip).  A sequence only enqueues: on the caller's stream,
+// on the handle's second stream, or into a stream capture.  Every grid it launches with was sized by size_grids at the
+// API entry (tfx_launch.hpp), for the whole env range; the ticks it enqueues are added to the handle's counters as it
+// goes (a capture takes them back and adds them per replay: run_captured, tfx_hip.hip).
 #pragma once
 #include "tfx_clone.hpp"
 #include "tfx_launch.hpp"
@@ -87,7 +90,6 @@ struct SeqGuard {
     h->d = keep;
     h->split_half = -1;
     h->split_first = false;
-    h->size_only = false;
     if (forked) {  // (an error exit: best effort, the error being reported is the first one)
       const std::string first = g_err;
       (void)join();
@@ -96,13 +98,13 @@ struct SeqGuard {
   }
 };
 
-// the launches of one agent step, in order, on `st`
+// the launches of one agent step, in order, on `st`; its ticks are counted once all of them are enqueued
 // split: the ticks run as two halves of the env range, the second on the handle's own stream (as step_chunk does for
 // tfx_step; launched eagerly - a batch big enough to split is not bound by its launches)
 int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *areward, uint8_t *adone,
-                   hipStream_t st, long long &n_fused, long long &n_pair, bool split = false) {
+                   hipStream_t st, bool split = false) {
   Dev &d = h->d;
-  n_fused = n_pair = 0;
+  long long n_pair = 0;
   SeqGuard guard(h);
   if (h->ep.on) {
     // episodes (tfx_set_episodes): the envs whose last decision ended their episode restart, ahead of the ticks and
@@ -121,7 +123,7 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
     d.agent_mode = 1;
     d.accum_rewards = remi ? 0 : 1;
     const int rc = launch_res(h, n_ticks, st, 1, remi, aobs, areward, adone);
-    if (rc == TFX_OK) n_fused = n_ticks;
+    if (rc == TFX_OK) h->fused_ticks += n_ticks;
     return rc;
   }
   hipLaunchKernelGGL(k_agent_begin, dim3(1), dim3(1), 0, st, d, const_cast<int *>(d.agent_first));
@@ -132,13 +134,6 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
   int rc = TFX_OK;
   const Dev whole = h->d;
   if (split) {
-    h->size_only = true;  // (grids are sized for the whole range)
-    (void)launch_move_tt<true, true>(h, 0, nullptr);
-    (void)launch_move_tt<false, true>(h, 0, nullptr);
-    (void)launch_tail(h, 0, nullptr, true);
-    (void)launch_advance(h, 0, nullptr);
-    h->size_only = false;
-    (void)edge_grid(h);
     // (the second half's clock is copied on the CALLER's stream, ahead of the fork: copied on the second stream it
     // raced with the first half's kernels, which move the clock on - a new stream's first launch can take longer to
     // start than a small batch's whole pair)
@@ -171,15 +166,15 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
         // (k_tail evaluates the bound for the pair that follows it: only the first pair pays a launch of its own)
         const bool tail = tail_usable(h);
         if (rc == TFX_OK && !(tail && t > 0)) rc = launch_risk(h, t, st);
-        if (rc == TFX_OK) rc = launch_move_tt<true, true>(h, t, st, 0, tail);
+        if (rc == TFX_OK) rc = launch_move_tt(h, true, true, t, st, 0, tail);
         if (rc == TFX_OK && tail) {
           // the rest of the pair in one launch (the envs k_risk sorted out get their second tick inside it)
           rc = launch_tail(h, t, st, true, (t + 3 < n_ticks ? TAIL_RISK_NEXT : 0) | (t + 2 >= n_ticks ? TAIL_LAST : 0));
         } else {
           if (rc == TFX_OK) rc = launch_advance(h, t, st);
           if (rc == TFX_OK) rc = launch_inputs(h, st);
-          if (rc == TFX_OK) rc = launch_edge<true>(h, t + 1, st);
-          if (rc == TFX_OK) rc = launch_move_tt<false, true>(h, t + 1, st, 1);
+          if (rc == TFX_OK) rc = launch_edge(h, true, t + 1, st);
+          if (rc == TFX_OK) rc = launch_move_tt(h, false, true, t + 1, st, 1);
           if (rc == TFX_OK) rc = launch_advance(h, t + 1, st);
         }
         if (rc == TFX_OK) n_pair += 2;
@@ -187,7 +182,7 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
       }
       for (; t < n_ticks && t < t0 + 2 && rc == TFX_OK; ++t) {
         rc = launch_inputs(h, st);
-        if (rc == TFX_OK) rc = (tt && !single_tick_ts(h)) ? launch_move_tt<false, true>(h, t, st) : launch_move(h, t, st);
+        if (rc == TFX_OK) rc = (tt && !single_tick_ts(h)) ? launch_move_tt(h, false, true, t, st) : launch_move(h, t, st);
         if (rc == TFX_OK) rc = launch_advance(h, t, st);
       }
     }
@@ -207,6 +202,8 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
                        areward, adone, d.agent_first, h->ep);
     HIPCHK(hipGetLastError());
   }
+  h->pair_ticks += n_pair;
+  if (split) h->split_ticks += n_ticks;
   return TFX_OK;
 }
 
@@ -227,7 +224,7 @@ int step_range(tfx_handle h, int n_ticks, hipStream_t st, int t_lo = 0, int t_hi
       if (timed) HIPCHK(hipEventRecord(e[0], st));
       // (from a call's second pair on the pass reads the road state words the k_tail before it left; the last k_tail
       // of the call stores leading / lastcar / hb themselves)
-      if (int rc = launch_move_tt<true>(h, t, st, 0, tail_usable(h), t > 0)) return rc;
+      if (int rc = launch_move_tt(h, true, false, t, st, 0, tail_usable(h), t > 0)) return rc;
       if (timed) HIPCHK(hipEventRecord(e[1], st));
       if (tail_usable(h)) {
         if (int rc = launch_tail(h, t, st, false, (t + 2 >= n_ticks ? TAIL_LAST : 0) | (t + 3 >= n_ticks ? TAIL_SYNC : 0))) return rc;
@@ -235,7 +232,7 @@ int step_range(tfx_handle h, int n_ticks, hipStream_t st, int t_lo = 0, int t_hi
       } else {
         if (int rc = launch_advance(h, t, st)) return rc;
         if (int rc = launch_inputs(h, st)) return rc;
-        if (int rc = launch_edge<false>(h, t + 1, st)) return rc;
+        if (int rc = launch_edge(h, false, t + 1, st)) return rc;
         if (int rc = launch_advance(h, t + 1, st)) return rc;
       }
       if (timed) {
@@ -251,7 +248,7 @@ int step_range(tfx_handle h, int n_ticks, hipStream_t st, int t_lo = 0, int t_hi
     hipEvent_t *e = timed ? &h->ev[(size_t)h->ev_used * 3] : nullptr;
     if (int rc = launch_inputs(h, st)) return rc;
     if (timed) HIPCHK(hipEventRecord(e[0], st));
-    if (int rc = (tt && !single_tick_ts(h)) ? launch_move_tt<false>(h, t, st) : launch_move(h, t, st)) return rc;
+    if (int rc = (tt && !single_tick_ts(h)) ? launch_move_tt(h, false, false, t, st) : launch_move(h, t, st)) return rc;
     if (timed) HIPCHK(hipEventRecord(e[1], st));
     if (int rc = launch_advance(h, t, st)) return rc;
     if (timed) {
@@ -270,14 +267,6 @@ int step_chunk(tfx_handle h, int n_ticks, hipStream_t st) {
   if (split_usable(h, n_ticks)) {
     // fork: the handle's own stream takes the second half of the envs, the caller's stream the first
     if (int rc = ensure_split(h, st)) return rc;
-    if (h->grid_tt[1] == 0 || h->grid_tt[0] == 0 || h->grid_tail == 0) {  // grids are sized for the whole range
-      h->size_only = true;
-      (void)launch_move_tt<true>(h, 0, nullptr);
-      (void)launch_move_tt<false>(h, 0, nullptr);
-      (void)launch_tail(h, 0, nullptr);
-      (void)launch_advance(h, 0, nullptr);
-      h->size_only = false;
-    }
     SeqGuard guard(h);
     const Dev whole = h->d;
     const int n0 = whole.E / 2;
