@@ -7,11 +7,13 @@
 //   * otherwise per-tick kernels, from two ticks on as PAIRS:
 //       k_move_tt (tfx_move_tt.hpp)   the cars through two ticks per trip through HBM
 //       k_tail (tfx_tail.hpp)         advance of tick t, the deferred cars' tick t+1, advance of t+1: a workgroup per env
-//     with the env range in two halves on two streams (tfx_sequence.hpp; validate mode: the W forms of both kernels,
-//     heterogeneous cars: the HET forms); small launches and the ring layout: k_move_t / k_move_ts / k_move_dma /
-//     k_move<WPR> + k_advance.
+//     with the env range in two halves on two streams (validate mode: the W forms of both kernels, heterogeneous cars:
+//     the HET forms); small launches and the ring layout: k_move_t / k_move_ts / k_move_dma / k_move<WPR> + k_advance.
+//     Plain calls and agent steps enqueue them through ONE sequence (tfx_sequence.hpp: pair, single, run_ticks), which
+//     lists where the two differ.
 // This file is the C ABI itself; the handle is in tfx_handle.hpp, kernel choice, grid sizing and launches in tfx_launch.hpp,
-// the launch sequences of tfx_step / tfx_agent_step in tfx_sequence.hpp, the cold kernels in tfx_misc.hpp.
+// the cold kernels in tfx_misc.hpp.  tfx_step and tfx_agent_step read alike: size the grids, decide, run the body
+// (step_body / agent_sequence) on the caller's stream or replay its capture (run_captured).
 #include <cmath>
 #include <new>
 
@@ -99,28 +101,33 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
   if (!res_usable(h, n_ticks)) {
     if (int rc = size_grids(h, true, n_ticks)) return rc;
   }
-  // a batch whose halves still fill the chip: two halves on two streams (k_tail of one under the pass of the other)
-  // (decisions split later than plain calls: fused 10-tick decisions at cfg2, us, two halves / one range - the captured
-  // graph: 384 envs 715 / 687, 448 747 / 726, 512 808 / 796-807, 768 1064 / 1019-1064, 1024 1251 / 1256, 4096 4380 / 4500 -
-  // from two envs per CU and half on)
-  const bool split = !res_usable(h, n_ticks) && !h->poisson && split_usable(h, n_ticks) &&
-                     (h->split == 2 || h->d.E / 2 >= 2 * h->n_cu);
+  // a batch whose halves still fill the chip: two halves on two streams (k_tail of one under the pass of the other),
+  // run eagerly; every other decision replays a captured graph
+  const bool split = split_usable(h, n_ticks, true);
   if (split) {
     if (int rc = ensure_split(h, st)) return rc;
   }
-  if (!h->use_graph || split) return agent_sequence(h, n_ticks, remi, aobs, areward, adone, st, split);
+  const bool capture = h->use_graph && !split;
+  auto body = [&](hipStream_t s) { return agent_sequence(h, n_ticks, remi, aobs, areward, adone, s, split); };
+  if (!capture) return body(st);
   // one graph per distinct launch sequence: everything baked into kernel arguments is in the key
   char key[1280];
   graph_key(h, key, sizeof key, n_ticks, remi, aobs, areward, adone);
-  return run_captured(h, h->captured[SEQ_AGENT], key, st, [&](hipStream_t cs) {
-    return agent_sequence(h, n_ticks, remi, aobs, areward, adone, cs);
-  });
+  return run_captured(h, h->captured[SEQ_AGENT], key, st, body);
 }
 
 namespace {
 
 // the launches of a tfx_step call on the per-tick kernels, on `st`
 int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
+  // a call's ticks, or one chunk of them: two halves on two streams where that pays (a chunk that splits is not captured)
+  auto ticks = [&](int n) {
+    const bool split = split_usable(h, n);
+    if (split) {
+      if (int rc = ensure_split(h, st)) return rc;
+    }
+    return run_ticks(h, n, st, false, split);
+  };
   if (int rc = launch_greedy(h, st)) return rc;  // (the decision of the call's first tick; later ones: advance_item)
   if (h->poisson && n_ticks > 0) {
     // the arrivals of the whole call (in chunks of the rows the count buffer holds) in ONE launch each: they depend
@@ -137,7 +144,7 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
       h->d.spawn_stride = (long)h->d.E * h->d.n_entry;
       if (rows) h->d.spawn_arch_stride = (long)h->d.E * h->d.n_entry * h->prow.S;
       if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
-      if (rc == TFX_OK) rc = step_chunk(h, chunk, st);
+      if (rc == TFX_OK) rc = ticks(chunk);
       h->d.spawn_stride = 0;
       if (rows) h->d.spawn_arch_stride = 0;
       h->d.action = act0;
@@ -145,7 +152,7 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
     }
     return rc;
   }
-  return step_chunk(h, n_ticks, st);
+  return ticks(n_ticks);
 }
 
 }  // namespace
@@ -705,50 +712,27 @@ int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   // envs that fit a compute unit's LDS: all the ticks of the call in one launch (tfx_resident.hpp)
   if (n_ticks > 0 && res_usable(h, n_ticks)) {
-    const bool timed = h->prof && h->ev_used < h->ev_ticks;
-    hipEvent_t *e = timed ? &h->ev[(size_t)h->ev_used * 3] : nullptr;
-    if (timed) HIPCHK(hipEventRecord(e[0], st));
+    TickTimer timer(h);
+    if (int rc = timer.begin(st)) return rc;
     if (int rc = launch_res(h, n_ticks, st)) return rc;
     h->fused_ticks += n_ticks;
-    if (timed) {
-      HIPCHK(hipEventRecord(e[1], st));
-      HIPCHK(hipEventRecord(e[2], st));
-      h->ev_weight[h->ev_used] = n_ticks;
-      ++h->ev_used;
-    }
-    return TFX_OK;
+    if (int rc = timer.mid(st)) return rc;
+    return timer.end(st, n_ticks);
   }
   if (int rc = size_grids(h, false, n_ticks)) return rc;
   // Launch-bound handles (a few thousand tiles: cfg4 x 16, a 16x16 grid x 256 envs) replay the call's launches as a HIP
   // graph, like the fused agent step does: at cfg4 x 16 the kernels of a tick add up to 59 us of its 65.6
   // (profiles/r04_cfg4_closed_loop_trace.txt).  Not while kernels are timed, not for calls that split over two streams.
   const Dev &d = h->d;
-  if (h->use_graph && !h->prof && n_ticks >= 4 && d.layout == 1 && (long)d.E * d.G <= (long)h->n_cu * 24 &&
-      !split_usable(h, n_ticks)) {
-    // captured once per distinct sequence (graph_key), replayed afterwards
-    char key[1280];
-    graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
-    return run_captured(h, h->captured[SEQ_STEP], key, st, [&](hipStream_t cs) { return step_body(h, n_ticks, cs); });
-  }
-  return step_body(h, n_ticks, st);
+  const bool capture = h->use_graph && !h->prof && n_ticks >= 4 && d.layout == 1 &&
+                       (long)d.E * d.G <= (long)h->n_cu * 24 && !split_usable(h, n_ticks);
+  auto body = [&](hipStream_t s) { return step_body(h, n_ticks, s); };
+  if (!capture) return body(st);
+  // captured once per distinct sequence (graph_key), replayed afterwards
+  char key[1280];
+  graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
+  return run_captured(h, h->captured[SEQ_STEP], key, st, body);
 }
-
-}  // extern "C"
-
-namespace {
-
-// workgroups of a k_measure launch over E * G (env, tile) items (tfx_measure.hpp); cap > 0: TFX_MEASURE_GRID
-long measure_grid(int E, int G, int n_cu, int cap_env) {
-  const long items = (long)E * G;
-  long grid = (items + 3) / 4;
-  const long cap = cap_env > 0 ? (long)cap_env : (long)n_cu * 16;
-  if (grid > cap) grid = cap;
-  return grid < 1 ? 1 : grid;
-}
-
-}  // namespace
-
-extern "C" {
 
 int tfx_move_cars(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
@@ -1011,7 +995,7 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
     o.s_greedy = src->d.greedy_act;
   }
   TFX_INJECT(dst);
-  hipLaunchKernelGGL(k_clone<false>, dim3(clone_grid(dst)), dim3(256), 0, (hipStream_t)stream, dst->d, src->d,
+  hipLaunchKernelGGL(k_clone<false>, dim3((unsigned)tile_grid(dst)), dim3(256), 0, (hipStream_t)stream, dst->d, src->d,
                      (const int *)src_of_env, o);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -1058,17 +1042,16 @@ int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_me
   o.queue = out->queue;
   o.speed_sum = out->speed_sum;
   o.accumulate = (flags & TFX_MEASURE_ACCUMULATE) ? 1 : 0;
-  // a wavefront per (env, tile), four to a workgroup; a few workgroups per compute unit stride over more (as k_clone).
   // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
-  hipLaunchKernelGGL(k_measure, dim3((unsigned)measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid)), dim3(256), 0,
-                     (hipStream_t)stream, h->d, halt_speed, x_from, o);
+  hipLaunchKernelGGL(k_measure, dim3((unsigned)tile_grid(h, true)), dim3(256), 0, (hipStream_t)stream, h->d, halt_speed,
+                     x_from, o);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
 
 int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
-  const long g = measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid);
+  const long g = tile_grid(h, true);
   if (grid) *grid = (int32_t)g;
   if (waves) *waves = (int32_t)(g * 4);
   return TFX_OK;
@@ -1097,9 +1080,9 @@ int tfx_road_cells(tfx_handle h, const float *edges, int32_t n_cells, const tfx_
   o.n_cars = out->n_cars;
   o.speed_sum = out->speed_sum;
   o.accumulate = (flags & TFX_CELLS_ACCUMULATE) ? 1 : 0;
-  // k_measure's launch (a wavefront per (env, tile), four to a workgroup, the same cap), instantiated on the cell bound.
+  // k_measure's launch (tile_grid), instantiated on the cell bound.
   // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
-  const dim3 grid((unsigned)measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid));
+  const dim3 grid((unsigned)tile_grid(h, true));
   const int B = n_cells;
   if (B <= 8)
     hipLaunchKernelGGL(k_cells<8>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
@@ -1115,7 +1098,7 @@ int tfx_cells_launch(tfx_handle h, int32_t n_cells, int32_t *grid, int32_t *wave
   if (int rc = check_handle(h, false)) return rc;
   if (n_cells < 1 || n_cells > TFX_MAX_CELLS)
     return fail(TFX_EINVAL, "cells: n_cells %d is outside 1..%d", n_cells, TFX_MAX_CELLS);
-  const long g = measure_grid(h->d.E, h->d.G, h->n_cu, h->measure_grid);
+  const long g = tile_grid(h, true);
   if (grid) *grid = (int32_t)g;
   if (waves) *waves = (int32_t)(g * 4);
   return TFX_OK;

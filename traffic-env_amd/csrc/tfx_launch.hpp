@@ -138,6 +138,16 @@ int grid_for(long items, int n_cu) {
   return (int)g;
 }
 
+// Grid of the kernels that take a wavefront per (env, tile), four to a workgroup (k_clone, k_measure, k_cells): a few
+// workgroups per compute unit stride over more; TFX_MEASURE_GRID caps the measures' and the cells' launches instead
+// (tests of their stride loops)
+long tile_grid(const tfx_handle_s *h, bool measure = false) {
+  long grid = ((long)h->d.E * h->d.G + 3) / 4;
+  const long cap = measure && h->measure_grid > 0 ? (long)h->measure_grid : (long)h->n_cu * 16;
+  if (grid > cap) grid = cap;
+  return grid < 1 ? 1 : grid;
+}
+
 // The on-device Poisson stream for the next n_ticks ticks (rows of the count buffer); one workgroup per env, as
 // many lanes as the burst is long (cfg4: thousands of cars per tick).
 int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
@@ -492,14 +502,20 @@ bool tail_usable(tfx_handle h, bool upfront = false) {
 // Two halves on two streams: where each half still runs pairs with k_tail behind them (one env per CU and half).
 // Measured at cfg2, ms per tick, one range / two halves: 4096 envs 0.474 / 0.437, 2048 0.238 / 0.227, 1024
 // 0.128 / 0.121, 512 0.0759 / 0.0705.  Not while per-kernel timing is on (tfx_profile times launches that own
-// the chip).
-bool split_usable(tfx_handle h, int n_ticks) {
+// the chip).  agent: the call is an agent step - not with k_res, not with arrivals produced tick by tick, and later
+// than plain calls.
+bool split_usable(tfx_handle h, int n_ticks, bool agent = false) {
   if (!h->split || h->prof || n_ticks < 2 || !pairs_usable(h, n_ticks) || !tail_usable(h)) return false;
   if (h->d.E < 2) return false;
+  if (agent && (res_usable(h, n_ticks) || h->poisson)) return false;
   if (h->split == 2) return true;
   // (round 4, us per tick, two halves / one range: 288 envs 61.7 / 47.6, 320 52.3 / 52.5, 352 63.6 / 52.4, 384 56.8 / 62.3,
   // 448 60.9 / 66.3, 512 64.3 / 71.4, 768 84.8 / 93.4: from three quarters of an env per CU and half on)
-  return h->d.E / 2 >= h->n_cu * 3 / 4 && (long)(h->d.E / 2) * h->d.G >= (long)h->n_cu * 4;
+  if (h->d.E / 2 < h->n_cu * 3 / 4 || (long)(h->d.E / 2) * h->d.G < (long)h->n_cu * 4) return false;
+  // (decisions: fused 10-tick decisions at cfg2, us, two halves / one range - the captured graph: 384 envs 715 / 687,
+  // 448 747 / 726, 512 808 / 796-807, 768 1064 / 1019-1064, 1024 1251 / 1256, 4096 4380 / 4500 - from two envs per CU
+  // and half on)
+  return !agent || h->d.E / 2 >= 2 * h->n_cu;
 }
 
 // k_tail<GREEDY, AGENT, W, HET>, with the env's ring words as its dynamic LDS

@@ -1,23 +1,25 @@
-// tfx_sequence.hpp - the launch sequences of tfx_step and tfx_agent_step: pairs of ticks, the env range in two halves on
-// two streams, the agent step (host side; included by tfx_hip.hip).  A sequence only enqueues: on the caller's stream,
-// on the handle's second stream, or into a stream capture.  Every grid it launches with was sized by size_grids at the
-// API entry (tfx_launch.hpp), for the whole env range; the ticks it enqueues are added to the handle's counters as it
-// goes (a capture takes them back and adds them per replay: run_captured, tfx_hip.hip).
+// tfx_sequence.hpp - the ONE launch sequence of the per-tick kernels, for plain tfx_step calls and agent steps alike
+// (host side; included by tfx_hip.hip):
+//   pair       the launches of two ticks - the only place that names their order
+//   single     the launches of one tick
+//   run_ticks  the loop over a call's ticks: pairs, then the odd tick; the env range in two halves on two streams
+//   agent_sequence  what a decision launches around its ticks (tfx_step's counterpart, step_body, is in tfx_hip.hip)
+// Where an agent step (tfx_agent_step, `if done: break`) differs from a plain call it says `agent`:
+//   k_risk     ahead of the pass of an agent step's pair, unless a k_tail before it evaluated the bound; never in a plain call
+//   the pass   a plain call's reads the road state words of the k_tail before it (rsw) from its second pair on; never an agent's
+//   k_tail     agent: TAIL_RISK_NEXT while another pair follows; plain: TAIL_SYNC on the call's last pair; both: TAIL_LAST
+//   no k_tail  agent: the restricted one-tick pass (the envs k_risk sorted out) between the edge and the second advance
+//   timing     tfx_profile times plain calls only (TickTimer)
+//   counters   tfx_tail_ticks counts plain calls only; pair, split and fused ticks count for both
+// A sequence only enqueues: on the caller's stream, on the handle's second stream, or into a stream capture.  Every grid
+// it launches with was sized by size_grids at the API entry (tfx_launch.hpp), for the whole env range; the ticks it
+// enqueues are added to the handle's counters as their pair is enqueued - a call that fails midway keeps those of the
+// pairs it had enqueued (a capture takes them back and adds them per replay: run_captured, tfx_hip.hip).
 #pragma once
 #include "tfx_clone.hpp"
 #include "tfx_launch.hpp"
 
 namespace {
-
-// workgroups of a k_clone launch: a wavefront per (destination env, tile), four to a workgroup; a few workgroups per
-// compute unit stride over more
-unsigned clone_grid(tfx_handle dst) {
-  const long items = (long)dst->d.E * dst->d.G;
-  long grid = (items + 3) / 4;
-  const long cap = (long)dst->n_cu * 16;
-  if (grid > cap) grid = cap;
-  return (unsigned)(grid < 1 ? 1 : grid);
-}
 
 // The masked restart of a decision from the attached pool (tfx_set_episode_pool): what tfx_clone_envs(h, pool, src, 0)
 // does with src[env] = the slot of rule 3 for the marked envs and -1 for the others, the source picked in the kernel
@@ -30,7 +32,7 @@ int launch_pool_restart(tfx_handle h, hipStream_t st) {
     o.d_greedy = h->d.greedy_act;
     o.s_greedy = pool->d.greedy_act;
   }
-  hipLaunchKernelGGL(k_clone<true>, dim3(clone_grid(h)), dim3(256), 0, st, h->d, pool->d, (const int *)nullptr, o);
+  hipLaunchKernelGGL(k_clone<true>, dim3((unsigned)tile_grid(h)), dim3(256), 0, st, h->d, pool->d, (const int *)nullptr, o);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
@@ -98,13 +100,141 @@ struct SeqGuard {
   }
 };
 
-// the launches of one agent step, in order, on `st`; its ticks are counted once all of them are enqueued
-// split: the ticks run as two halves of the env range, the second on the handle's own stream (as step_chunk does for
-// tfx_step; launched eagerly - a batch big enough to split is not bound by its launches)
+// Per-kernel timing of plain calls (tfx_profile): three events per timed entry - ahead of the mover, behind it, behind
+// the entry's last launch - and the ticks the entry covers.  Active while the handle times and has entries left when
+// begin() is asked; does nothing otherwise.
+struct TickTimer {
+  tfx_handle h;
+  hipEvent_t *e = nullptr;
+  explicit TickTimer(tfx_handle hh) : h(hh) {}
+  int begin(hipStream_t st) {
+    if (!h->prof || h->ev_used >= h->ev_ticks) return TFX_OK;
+    e = &h->ev[(size_t)h->ev_used * 3];
+    HIPCHK(hipEventRecord(e[0], st));
+    return TFX_OK;
+  }
+  int mid(hipStream_t st) {
+    if (e) HIPCHK(hipEventRecord(e[1], st));
+    return TFX_OK;
+  }
+  int end(hipStream_t st, int weight) {
+    if (!e) return TFX_OK;
+    HIPCHK(hipEventRecord(e[2], st));
+    h->ev_weight[h->ev_used] = weight;
+    ++h->ev_used;
+    return TFX_OK;
+  }
+};
+
+// Ticks t and t + 1 of a call (a chunk) of n_ticks ticks, of the envs h->d describes (the whole handle, or one half of
+// it), on st: a two-tick pass (tfx_move_tt.hpp) and the rest of the pair.
+int pair(tfx_handle h, int t, int n_ticks, hipStream_t st, bool agent) {
+  const bool tail = tail_usable(h);
+  TickTimer timer(h);
+  if (int rc = launch_inputs(h, st)) return rc;
+  // agent steps: envs in which the first tick of a pair could overflow take the pair one tick at a time (k_risk; k_tail
+  // evaluates the bound for the pair that follows it: only the first pair pays a launch of its own)
+  if (agent && !(tail && t > 0)) {
+    if (int rc = launch_risk(h, t, st)) return rc;
+  }
+  if (!agent) {
+    if (int rc = timer.begin(st)) return rc;
+  }
+  // (plain calls: from a call's second pair on the pass reads the road state words the k_tail before it left; the last
+  // k_tail of the call stores leading / lastcar / hb themselves)
+  if (int rc = launch_move_tt(h, true, agent, t, st, 0, tail, agent ? false : t > 0)) return rc;
+  if (int rc = timer.mid(st)) return rc;
+  if (tail) {
+    // the rest of the pair in one launch (agent: the envs k_risk sorted out get their second tick inside it)
+    const int flags = (t + 2 >= n_ticks ? TAIL_LAST : 0) |
+                      (agent ? (t + 3 < n_ticks ? TAIL_RISK_NEXT : 0) : (t + 3 >= n_ticks ? TAIL_SYNC : 0));
+    if (int rc = launch_tail(h, t, st, agent, flags)) return rc;
+    if (!agent) h->tail_ticks += 2;
+  } else {
+    if (int rc = launch_advance(h, t, st)) return rc;
+    if (int rc = launch_inputs(h, st)) return rc;
+    if (int rc = launch_edge(h, agent, t + 1, st)) return rc;
+    if (agent) {
+      if (int rc = launch_move_tt(h, false, true, t + 1, st, /*only_risky=*/1)) return rc;
+    }
+    if (int rc = launch_advance(h, t + 1, st)) return rc;
+  }
+  if (int rc = timer.end(st, 2)) return rc;
+  h->pair_ticks += 2;
+  return TFX_OK;
+}
+
+// Tick t alone.  A handle that runs its calls as pairs takes the one-tick form of the pass, or k_move_ts where the
+// launch is small enough for it (single_tick_ts)
+int single(tfx_handle h, int t, hipStream_t st, bool agent) {
+  TickTimer timer(h);
+  if (int rc = launch_inputs(h, st)) return rc;
+  if (!agent) {
+    if (int rc = timer.begin(st)) return rc;
+  }
+  if (int rc = (pairs_usable(h) && !single_tick_ts(h)) ? launch_move_tt(h, false, agent, t, st) : launch_move(h, t, st)) return rc;
+  if (int rc = timer.mid(st)) return rc;
+  if (int rc = launch_advance(h, t, st)) return rc;
+  return timer.end(st, 1);
+}
+
+// The ticks of a call (of one chunk of a tfx_step call) on the per-tick kernels, on st: pairs, then the odd tick.
+// split (split_usable; ensure_split has run): the env range in two halves, the handle's own stream takes the second
+// half of the envs, the caller's stream the first - launched eagerly: a batch big enough to split is not bound by its
+// launches.
+int run_ticks(tfx_handle h, int n_ticks, hipStream_t st, bool agent, bool split) {
+  SeqGuard guard(h);
+  const Dev whole = h->d;
+  Dev halves[2] = {whole, whole};
+  if (split) {
+    // (the second half's clock is copied on the CALLER's stream, ahead of the fork: copied on the second stream it
+    // raced with the first half's kernels, which move the clock on - a new stream's first launch can take longer to
+    // start than a small batch's whole pair)
+    hipLaunchKernelGGL(k_clock_copy, dim3(1), dim3(1), 0, st, whole.tickA, whole.tickB, h->tick2);
+    HIPCHK(hipGetLastError());
+    if (int rc = guard.fork(st)) return rc;
+    const int n0 = whole.E / 2;
+    halves[0] = sub_dev(h, 0, n0, nullptr);
+    halves[1] = sub_dev(h, n0, whole.E - n0, h->tick2);
+  }
+  // The two halves' launches are submitted pair by pair, alternately.  (Submitted half after half - all of the first
+  // half's launches, then the second's - the second stream's first launch reached the device only after the host had
+  // queued the whole first half: under rocprofv3 the first half ran FIVE pairs alone at the start of a 50-tick call
+  // and the second five alone at its end, each at 0.47 ms per half pair instead of the 0.39 of two halves side by
+  // side; profiles/r04_split_submission_order.txt.)  One range: all its ticks in one turn.
+  const long long pair0 = h->pair_ticks, tail0 = h->tail_ticks;
+  const int turn = split ? 2 : n_ticks;
+  int rc = TFX_OK;
+  for (int t0 = 0; t0 < n_ticks && rc == TFX_OK; t0 += turn) {
+    for (int half = 0; half < (split ? 2 : 1) && rc == TFX_OK; ++half) {
+      if (split) {
+        h->d = halves[half];
+        h->split_half = half;
+        h->split_first = t0 == 0;
+      }
+      const hipStream_t hs = half == 0 ? st : h->split_stream;
+      const int t_hi = t0 + turn < n_ticks ? t0 + turn : n_ticks;
+      int t = t0;
+      if (pairs_usable(h))
+        for (; t + 1 < t_hi && rc == TFX_OK; t += 2) rc = pair(h, t, n_ticks, hs, agent);
+      for (; t < t_hi && rc == TFX_OK; ++t) rc = single(h, t, hs, agent);
+    }
+  }
+  if (!split) return rc;
+  h->d = whole;
+  h->split_half = -1;
+  h->pair_ticks = pair0 + (h->pair_ticks - pair0) / 2;  // (both halves counted them)
+  h->tail_ticks = tail0 + (h->tail_ticks - tail0) / 2;
+  if (rc != TFX_OK) return rc;  // (the guard joins the second stream)
+  h->split_ticks += n_ticks;
+  return guard.join();
+}
+
+// the launches of one agent step, in order, on `st`: the episode restart, then k_res with the decision's tail inside, or
+// the per-tick kernels between k_agent_begin and k_agent_tail
 int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *areward, uint8_t *adone,
-                   hipStream_t st, bool split = false) {
+                   hipStream_t st, bool split) {
   Dev &d = h->d;
-  long long n_pair = 0;
   SeqGuard guard(h);
   if (h->ep.on) {
     // episodes (tfx_set_episodes): the envs whose last decision ended their episode restart, ahead of the ticks and
@@ -131,172 +261,15 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
   if (int rc = launch_greedy(h, st)) return rc;
   d.agent_mode = 1;
   d.accum_rewards = remi ? 0 : 1;
-  int rc = TFX_OK;
-  const Dev whole = h->d;
-  if (split) {
-    // (the second half's clock is copied on the CALLER's stream, ahead of the fork: copied on the second stream it
-    // raced with the first half's kernels, which move the clock on - a new stream's first launch can take longer to
-    // start than a small batch's whole pair)
-    hipLaunchKernelGGL(k_clock_copy, dim3(1), dim3(1), 0, st, whole.tickA, whole.tickB, h->tick2);
-    HIPCHK(hipGetLastError());
-    if (int frc = guard.fork(st)) return frc;
-  }
-  hipStream_t user_st = st;
-  // (the halves' launches are submitted pair by pair, alternately: see step_chunk)
-  Dev halves[2] = {whole, whole};
-  if (split) {
-    const int n0 = whole.E / 2;
-    halves[0] = sub_dev(h, 0, n0, nullptr);
-    halves[1] = sub_dev(h, n0, whole.E - n0, h->tick2);
-  }
-  for (int t0 = 0; t0 < n_ticks && rc == TFX_OK; t0 += 2) {
-    for (int half = 0; half < (split ? 2 : 1) && rc == TFX_OK; ++half) {
-      if (split) {
-        h->d = halves[half];
-        st = half == 0 ? user_st : h->split_stream;
-        h->split_half = half;
-        h->split_first = t0 == 0;
-      }
-      const bool tt = pairs_usable(h);
-      int t = t0;
-      if (tt && t + 1 < n_ticks) {
-        // a two-tick pass (tfx_move_tt.hpp); envs in which the first tick of a pair could overflow take the pair one
-        // tick at a time (k_risk)
-        rc = launch_inputs(h, st);
-        // (k_tail evaluates the bound for the pair that follows it: only the first pair pays a launch of its own)
-        const bool tail = tail_usable(h);
-        if (rc == TFX_OK && !(tail && t > 0)) rc = launch_risk(h, t, st);
-        if (rc == TFX_OK) rc = launch_move_tt(h, true, true, t, st, 0, tail);
-        if (rc == TFX_OK && tail) {
-          // the rest of the pair in one launch (the envs k_risk sorted out get their second tick inside it)
-          rc = launch_tail(h, t, st, true, (t + 3 < n_ticks ? TAIL_RISK_NEXT : 0) | (t + 2 >= n_ticks ? TAIL_LAST : 0));
-        } else {
-          if (rc == TFX_OK) rc = launch_advance(h, t, st);
-          if (rc == TFX_OK) rc = launch_inputs(h, st);
-          if (rc == TFX_OK) rc = launch_edge(h, true, t + 1, st);
-          if (rc == TFX_OK) rc = launch_move_tt(h, false, true, t + 1, st, 1);
-          if (rc == TFX_OK) rc = launch_advance(h, t + 1, st);
-        }
-        if (rc == TFX_OK) n_pair += 2;
-        t += 2;
-      }
-      for (; t < n_ticks && t < t0 + 2 && rc == TFX_OK; ++t) {
-        rc = launch_inputs(h, st);
-        if (rc == TFX_OK) rc = (tt && !single_tick_ts(h)) ? launch_move_tt(h, false, true, t, st) : launch_move(h, t, st);
-        if (rc == TFX_OK) rc = launch_advance(h, t, st);
-      }
-    }
-  }
-  if (split) h->d = whole;
-  h->split_half = -1;
-  st = user_st;
-  if (rc != TFX_OK) return rc;
-  if (split) {
-    n_pair /= 2;  // (both halves counted them)
-    if (int jrc = guard.join()) return jrc;
-  }
-  d.agent_mode = guard.keep.agent_mode;  // the tail kernels below run outside the step's tick loop
+  if (int rc = run_ticks(h, n_ticks, st, true, split)) return rc;
+  d.agent_mode = guard.keep.agent_mode;  // the tail kernel below runs outside the step's tick loop
   d.accum_rewards = guard.keep.accum_rewards;
   if (remi || aobs || areward || adone || h->ep.on) {
     hipLaunchKernelGGL(k_agent_tail, dim3(grid_for((long)d.E * (2 * d.r + d.I), h->n_cu)), dim3(256), 0, st, d, remi, aobs,
                        areward, adone, d.agent_first, h->ep);
     HIPCHK(hipGetLastError());
   }
-  h->pair_ticks += n_pair;
-  if (split) h->split_ticks += n_ticks;
   return TFX_OK;
 }
 
 }  // namespace
-
-namespace {
-// the per-tick kernels for ticks [t_lo, t_hi) of a call of n_ticks ticks (t_lo even; default: all of them) of the envs
-// h->d describes (the whole handle, or one half of it), on st
-int step_range(tfx_handle h, int n_ticks, hipStream_t st, int t_lo = 0, int t_hi = -1) {
-  if (t_hi < 0 || t_hi > n_ticks) t_hi = n_ticks;
-  int t = t_lo;
-  const bool tt = pairs_usable(h);
-  if (tt) {
-    for (; t + 1 < t_hi; t += 2) {
-      const bool timed = h->prof && h->ev_used < h->ev_ticks;
-      hipEvent_t *e = timed ? &h->ev[(size_t)h->ev_used * 3] : nullptr;
-      if (int rc = launch_inputs(h, st)) return rc;
-      if (timed) HIPCHK(hipEventRecord(e[0], st));
-      // (from a call's second pair on the pass reads the road state words the k_tail before it left; the last k_tail
-      // of the call stores leading / lastcar / hb themselves)
-      if (int rc = launch_move_tt(h, true, false, t, st, 0, tail_usable(h), t > 0)) return rc;
-      if (timed) HIPCHK(hipEventRecord(e[1], st));
-      if (tail_usable(h)) {
-        if (int rc = launch_tail(h, t, st, false, (t + 2 >= n_ticks ? TAIL_LAST : 0) | (t + 3 >= n_ticks ? TAIL_SYNC : 0))) return rc;
-        h->tail_ticks += 2;
-      } else {
-        if (int rc = launch_advance(h, t, st)) return rc;
-        if (int rc = launch_inputs(h, st)) return rc;
-        if (int rc = launch_edge(h, false, t + 1, st)) return rc;
-        if (int rc = launch_advance(h, t + 1, st)) return rc;
-      }
-      if (timed) {
-        HIPCHK(hipEventRecord(e[2], st));
-        h->ev_weight[h->ev_used] = 2;
-        ++h->ev_used;
-      }
-      h->pair_ticks += 2;
-    }
-  }
-  for (; t < t_hi; ++t) {
-    const bool timed = h->prof && h->ev_used < h->ev_ticks;
-    hipEvent_t *e = timed ? &h->ev[(size_t)h->ev_used * 3] : nullptr;
-    if (int rc = launch_inputs(h, st)) return rc;
-    if (timed) HIPCHK(hipEventRecord(e[0], st));
-    if (int rc = (tt && !single_tick_ts(h)) ? launch_move_tt(h, false, false, t, st) : launch_move(h, t, st)) return rc;
-    if (timed) HIPCHK(hipEventRecord(e[1], st));
-    if (int rc = launch_advance(h, t, st)) return rc;
-    if (timed) {
-      HIPCHK(hipEventRecord(e[2], st));
-      h->ev_weight[h->ev_used] = 1;
-      ++h->ev_used;
-    }
-  }
-  return TFX_OK;
-}
-
-}  // namespace
-
-// n_ticks ticks on the per-tick kernels, the env range in two halves on two streams where that pays
-int step_chunk(tfx_handle h, int n_ticks, hipStream_t st) {
-  if (split_usable(h, n_ticks)) {
-    // fork: the handle's own stream takes the second half of the envs, the caller's stream the first
-    if (int rc = ensure_split(h, st)) return rc;
-    SeqGuard guard(h);
-    const Dev whole = h->d;
-    const int n0 = whole.E / 2;
-    const long long pair0 = h->pair_ticks, tail0 = h->tail_ticks;
-    // (the clock copy runs on the caller's stream, ahead of the fork: see agent_sequence)
-    hipLaunchKernelGGL(k_clock_copy, dim3(1), dim3(1), 0, st, whole.tickA, whole.tickB, h->tick2);
-    HIPCHK(hipGetLastError());
-    if (int frc = guard.fork(st)) return frc;
-    int rc = TFX_OK;
-    // The two halves' launches are submitted pair by pair, alternately.  (Submitted half after half - all of the first
-    // half's launches, then the second's - the second stream's first launch reached the device only after the host had
-    // queued the whole first half: under rocprofv3 the first half ran FIVE pairs alone at the start of a 50-tick call
-    // and the second five alone at its end, each at 0.47 ms per half pair instead of the 0.39 of two halves side by
-    // side; profiles/r04_split_submission_order.txt.)
-    const Dev halves[2] = {sub_dev(h, 0, n0, nullptr), sub_dev(h, n0, whole.E - n0, h->tick2)};
-    for (int t = 0; t < n_ticks && rc == TFX_OK; t += 2) {
-      for (int half = 0; half < 2 && rc == TFX_OK; ++half) {
-        h->d = halves[half];
-        h->split_half = half;
-        h->split_first = t == 0;
-        rc = step_range(h, n_ticks, half == 0 ? st : h->split_stream, t, t + 2);
-      }
-    }
-    h->d = whole;
-    h->split_half = -1;
-    h->pair_ticks = pair0 + (h->pair_ticks - pair0) / 2;  // (both halves counted them)
-    h->tail_ticks = tail0 + (h->tail_ticks - tail0) / 2;
-    if (rc != TFX_OK) return rc;  // (the guard joins the second stream)
-    h->split_ticks += n_ticks;
-    return guard.join();
-  }
-  return step_range(h, n_ticks, st);
-}
