@@ -164,10 +164,23 @@ __device__ __forceinline__ void advance_item(const Dev &d, int env, int s, int t
   if (serial && s == 0) {
     if (TL) advance_env_serial_t<HET, WP>(d, env, tick, tidx);
     else advance_env_serial(d, env, tick, tidx);
-    if (decide)
+    if (decide) {
+      // The decisions go into the buffer THIS tick's action is read from (light_next: d.action is greedy_act).  So this
+      // lane stores the light words of every intersection of the env first - the lanes of the others leave theirs alone
+      // (below): a lane that read its action after this lane's decision took the next tick's, and the stored phase
+      // switched a tick before the cars saw it (found by tests/test_gpu_stride_rounds.py: ragged states take this path).
+      int *ob = d.lights + (size_t)env * d.lights_stride;
+      for (int i = 0; i < d.I; ++i) {
+        int ph_i, el_i;
+        light_update(d, env, i, tick, tidx, ph_i, el_i);
+        ob[i] = ph_i;
+        ob[d.I + i] = el_i;
+      }
       for (int i = 0; i < d.I; ++i) d.greedy_act[(size_t)env * d.I + i] = greedy_decide(d, env, i);
+    }
   }
   if (s < d.I) {
+    if (serial && decide) return;  // (the env's first lane has stored the light words, ahead of its decisions)
     int ph_new, el_new;
     light_update(d, env, s, tick, tidx, ph_new, el_new);
     if (!serial) {

@@ -144,6 +144,8 @@ struct tfx_handle_s {
   unsigned long long *clone_skipped = nullptr;
   // tfx_road_measures (tfx_measure.hpp): TFX_MEASURE_GRID=n caps its launch at n workgroups (tests of its stride loop)
   int measure_grid = 0;
+  // TFX_GRID_CAP=n (test hook): every launch of a kernel that strides over its work takes at most n workgroups (0: off)
+  int grid_cap = 0;
 };
 
 namespace {

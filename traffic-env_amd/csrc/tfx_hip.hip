@@ -212,6 +212,7 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   if (const char *gv = getenv("TFX_TT_SEG")) h->tt_seg = atoi(gv);
   if (const char *gv = getenv("TFX_TT_SEGS")) h->tt_segs = atoi(gv);
   if (const char *gv = getenv("TFX_MEASURE_GRID")) h->measure_grid = atoi(gv);
+  if (const char *gv = getenv("TFX_GRID_CAP")) h->grid_cap = atoi(gv) > 0 ? atoi(gv) : 0;
   if (const char *pc = getenv("TFX_MOVE_BLOCKS_PER_CU")) h->move_blocks_per_cu = atoi(pc);
   if (const char *sv = getenv("TFX_STAGGER")) h->stagger = atoi(sv) != 0;
   int dev = 0;
@@ -461,7 +462,7 @@ int tfx_reset(tfx_handle h, const int32_t *phase_init, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipMemsetAsync(h->d.tickA, 0, sizeof(int), st));
   HIPCHK(hipMemsetAsync(h->d.tickB, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_reset, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0, st, h->d, phase_init,
+  hipLaunchKernelGGL(k_reset, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0, st, h->d, phase_init,
                      (const uint8_t *)nullptr, h->ep);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -470,7 +471,7 @@ int tfx_reset(tfx_handle h, const int32_t *phase_init, void *stream) {
 int tfx_reset_envs(tfx_handle h, const int32_t *phase_init, const uint8_t *mask, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
   if (!phase_init || !mask) return fail(TFX_EINVAL, "phase_init and mask are required");
-  hipLaunchKernelGGL(k_reset, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_reset, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0, (hipStream_t)stream,
                      h->d, phase_init, mask, h->ep);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -505,7 +506,7 @@ int tfx_set_episodes(tfx_handle h, int32_t enabled, int32_t max_decisions, uint6
 
 int tfx_refresh(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
-  hipLaunchKernelGGL(k_refresh, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0,
+  hipLaunchKernelGGL(k_refresh, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0,
                      (hipStream_t)stream, h->d);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -750,7 +751,7 @@ int tfx_advance_finished_cars(tfx_handle h, void *stream) {
 
 int tfx_remi(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
-  hipLaunchKernelGGL(k_remi, dim3(grid_for((long)h->d.E * h->d.I, h->n_cu)), dim3(256), 0,
+  hipLaunchKernelGGL(k_remi, dim3(grid_for(h, (long)h->d.E * h->d.I)), dim3(256), 0,
                      (hipStream_t)stream, h->d);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -759,7 +760,7 @@ int tfx_remi(tfx_handle h, void *stream) {
 int tfx_cars_on_roads(tfx_handle h, int32_t *out, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
   if (!out) return fail(TFX_EINVAL, "out is null");
-  hipLaunchKernelGGL(k_cars_on_roads, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0,
+  hipLaunchKernelGGL(k_cars_on_roads, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0,
                      (hipStream_t)stream, h->d, out);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -768,7 +769,7 @@ int tfx_cars_on_roads(tfx_handle h, int32_t *out, void *stream) {
 int tfx_done(tfx_handle h, uint8_t *out, int32_t since_tick, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
   if (!out) return fail(TFX_EINVAL, "out is null");
-  hipLaunchKernelGGL(k_done, dim3(grid_for(h->d.E, h->n_cu)), dim3(256), 0, (hipStream_t)stream, h->d,
+  hipLaunchKernelGGL(k_done, dim3(grid_for(h, h->d.E)), dim3(256), 0, (hipStream_t)stream, h->d,
                      out, since_tick);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -857,7 +858,7 @@ int tfx_export_ring(tfx_handle h, float *ring_xv, float *ring_w, uint8_t *ring_a
   if (int rc = check_handle(h, true)) return rc;
   if (h->d.layout != 1) return fail(TFX_ESTATE, "the handle already uses the ring layout");
   if (!ring_xv) return fail(TFX_EINVAL, "ring_xv is null");
-  hipLaunchKernelGGL(k_export_ring, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0,
+  hipLaunchKernelGGL(k_export_ring, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0,
                      (hipStream_t)stream, h->d, reinterpret_cast<float2 *>(ring_xv), ring_w, ring_a);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -867,7 +868,7 @@ int tfx_import_ring(tfx_handle h, const float *ring_xv, const float *ring_w, con
   if (int rc = check_handle(h, true)) return rc;
   if (h->d.layout != 1) return fail(TFX_ESTATE, "the handle already uses the ring layout");
   if (!ring_xv) return fail(TFX_EINVAL, "ring_xv is null");
-  hipLaunchKernelGGL(k_import_ring, dim3(grid_for((long)h->d.E * h->d.R, h->n_cu)), dim3(256), 0,
+  hipLaunchKernelGGL(k_import_ring, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0,
                      (hipStream_t)stream, h->d, reinterpret_cast<const float2 *>(ring_xv), ring_w, ring_a);
   HIPCHK(hipGetLastError());
   return TFX_OK;

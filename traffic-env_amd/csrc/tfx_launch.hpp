@@ -38,6 +38,11 @@ struct Pick {
 using TickFn = void (*)(Dev, int);        // (d, tidx)
 using TickFn3 = void (*)(Dev, int, int);  // k_move_tt: (d, tidx, only_risky); k_tail: (d, tidx, flags)
 
+// TFX_GRID_CAP=n (test hook, read in tfx_create): at most n workgroups for every launch whose kernel strides over its
+// work, so that the later rounds of the stride loops run at test sizes.  Every grid the plan sizes goes through here;
+// 0 (the default) leaves each one as it is.
+long grid_capped(const tfx_handle_s *h, long grid) { return h->grid_cap > 0 && grid > h->grid_cap ? (long)h->grid_cap : grid; }
+
 // Grid of the move kernel: every block resident at once (occupancy query), a multiple of 8 so the
 // XCD-contiguous chunking applies, never more blocks than there is work.
 int move_grid(tfx_handle h, const Pick<TickFn> &p) {
@@ -53,7 +58,7 @@ int move_grid(tfx_handle h, const Pick<TickFn> &p) {
   long g = (long)h->n_cu * per_cu;
   if (g > need) g = need;
   if (g >= 8) g -= g % 8;
-  return (int)(g < 1 ? 1 : g);
+  return (int)grid_capped(h, g < 1 ? 1 : g);
 }
 
 // Transposed layout.  TFX_MOVE_VARIANT: 0 = automatic | 90 / 91 force / forbid the four-waves-per-tile kernel
@@ -130,22 +135,24 @@ Pick<TickFn> pick_move(const tfx_handle_s *h) {
   return pick_dma<66, 8, 2, 4, false, 2>(h);  // cfg2: best of the tuning runs
 }
 
-int grid_for(long items, int n_cu) {
+int grid_for(const tfx_handle_s *h, long items) {
   long g = (items + 255) / 256;
-  const long cap = (long)n_cu * 8;
+  const long cap = (long)h->n_cu * 8;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
-  return (int)g;
+  return (int)grid_capped(h, g);
 }
 
 // Grid of the kernels that take a wavefront per (env, tile), four to a workgroup (k_clone, k_measure, k_cells): a few
 // workgroups per compute unit stride over more; TFX_MEASURE_GRID caps the measures' and the cells' launches instead
-// (tests of their stride loops)
+// (tests of their stride loops; TFX_GRID_CAP caps the others, and these too where TFX_MEASURE_GRID is not set)
 long tile_grid(const tfx_handle_s *h, bool measure = false) {
   long grid = ((long)h->d.E * h->d.G + 3) / 4;
-  const long cap = measure && h->measure_grid > 0 ? (long)h->measure_grid : (long)h->n_cu * 16;
+  const bool own = measure && h->measure_grid > 0;
+  const long cap = own ? (long)h->measure_grid : (long)h->n_cu * 16;
   if (grid > cap) grid = cap;
-  return grid < 1 ? 1 : grid;
+  if (grid < 1) grid = 1;
+  return own ? grid : grid_capped(h, grid);
 }
 
 // The on-device Poisson stream for the next n_ticks ticks (rows of the count buffer); one workgroup per env, as
@@ -153,7 +160,7 @@ long tile_grid(const tfx_handle_s *h, bool measure = false) {
 int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
   const Dev &d = h->d;
   const int threads = d.E <= 64 ? 1024 : (d.E <= 1024 ? 256 : 64);
-  const int pg = d.E < h->n_cu * 16 ? d.E : h->n_cu * 16;
+  const int pg = (int)grid_capped(h, d.E < h->n_cu * 16 ? d.E : h->n_cu * 16);
   if (h->prow.rows)  // (heterogeneous cars: the archetype row of every car too, and a running count per entry road)
     hipLaunchKernelGGL(k_poisson<true>, dim3(pg), dim3(threads), ((size_t)2 * d.n_entry + 2) * sizeof(int), st, d, h->ps,
                        n_ticks, h->prow);
@@ -174,7 +181,7 @@ int launch_inputs(tfx_handle h, hipStream_t st) {
 
 int launch_greedy(tfx_handle h, hipStream_t st) {
   if (!h->greedy) return TFX_OK;
-  hipLaunchKernelGGL(k_greedy, dim3(grid_for((long)h->d.E * h->d.I, h->n_cu)), dim3(256), 0, st, h->d,
+  hipLaunchKernelGGL(k_greedy, dim3(grid_for(h, (long)h->d.E * h->d.I)), dim3(256), 0, st, h->d,
                      h->dev_greedy, h->greedy_spacing);
   HIPCHK(hipGetLastError());
   return TFX_OK;
@@ -561,7 +568,7 @@ int size_grids(tfx_handle h, bool agent, int n_ticks) {
     const Pick<TickFn> p = pick_move(h);
     if (int rc = raise_lds((const void *)p.fn, p.lds)) return rc;
     // (k_move_ts: a workgroup per tile, up to 8 per CU striding over more)
-    h->grid_move = p.items ? move_grid(h, p) : (int)(tiles < (long)h->n_cu * 8 ? tiles : (long)h->n_cu * 8);
+    h->grid_move = p.items ? move_grid(h, p) : (int)grid_capped(h, tiles < (long)h->n_cu * 8 ? tiles : (long)h->n_cu * 8);
   }
   if (h->grid_adv == 0) {
     // no more blocks than are resident at once (k_advance<true> holds 5 per CU): with 8 per CU launched the
@@ -571,7 +578,7 @@ int size_grids(tfx_handle h, bool agent, int n_ticks) {
     if (per_cu > 8) per_cu = 8;
     long g = (items + 255) / 256;
     if (g > (long)h->n_cu * per_cu) g = (long)h->n_cu * per_cu;
-    h->grid_adv = (int)(g < 1 ? 1 : g);
+    h->grid_adv = (int)grid_capped(h, g < 1 ? 1 : g);
   }
   if (!pairs_usable(h)) return TFX_OK;
   // k_move_tt.  Grid: 16 workgroups per CU, 6 of them resident at once: later rounds of workgroups even out the end of the launch.
@@ -597,7 +604,7 @@ int size_grids(tfx_handle h, bool agent, int n_ticks) {
     if (per_cu > 6) per_cu = 6;  // measured at cfg2, 4 / 5 / 6 / 7 blocks per CU: 0.112 / 0.102 / 0.097 / 0.118 ms
     long g = (long)h->n_cu * per_cu;
     if (g > (tiles + 3) / 4) g = (tiles + 3) / 4;
-    h->grid_edge = (int)(g < 1 ? 1 : g);
+    h->grid_edge = (int)grid_capped(h, g < 1 ? 1 : g);
   }
   // (tfx_step has generated its arrivals by the time its pairs are enqueued: step_body)
   if (n_ticks < 2 || !tail_usable(h, !agent)) return TFX_OK;
@@ -612,7 +619,7 @@ int size_grids(tfx_handle h, bool agent, int n_ticks) {
       const int threads = half ? 128 : 256;
       long g = (long)h->n_cu * per_cu_of(p.fn, threads, p.lds, 1);
       if (g > d.E) g = d.E;
-      (half ? h->grid_tail_half : h->grid_tail) = (int)(g < 1 ? 1 : g);
+      (half ? h->grid_tail_half : h->grid_tail) = (int)grid_capped(h, g < 1 ? 1 : g);
       (half ? h->tail_threads_half : h->tail_threads) = threads;
     }
   }
@@ -666,6 +673,7 @@ int launch_move_tt(tfx_handle h, bool two, bool agent, int tidx, hipStream_t st,
     const long groups = S == 2 ? (tiles + 1) / 2 : tiles;
     long grid = (long)h->n_cu * 16;  // (workgroups stride over the tiles)
     if (grid > groups) grid = groups;
+    grid = grid_capped(h, grid);
     const Pick<TickFn> p = pick_tts(S, d.w != nullptr, agent, crec, rsw);
     h->step_kernel = p.name;
     rc = launch(h, p, grid, st, tidx);
@@ -677,6 +685,7 @@ int launch_move_tt(tfx_handle h, bool two, bool agent, int tidx, hipStream_t st,
     if (grid > need) grid = need;
     if (grid >= 8) grid -= grid % 8;
     if (grid < 1) grid = 1;
+    grid = grid_capped(h, grid);
     const Pick<TickFn3> p = pick_tt(d, two, agent, crec, rsw);
     h->step_kernel = p.name;
     rc = launch(h, p, grid, st, tidx, only_risky);

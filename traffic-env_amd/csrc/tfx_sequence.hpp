@@ -244,7 +244,7 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
       // ... as clones of envs of the attached pool (tfx_set_episode_pool), in that same one launch
       if (int rc = launch_pool_restart(h, st)) return rc;
     } else {
-      hipLaunchKernelGGL(k_episode_begin, dim3(grid_for((long)d.E * d.R, h->n_cu)), dim3(256), 0, st, d, h->ep);
+      hipLaunchKernelGGL(k_episode_begin, dim3(grid_for(h, (long)d.E * d.R)), dim3(256), 0, st, d, h->ep);
       HIPCHK(hipGetLastError());
     }
   }
@@ -265,7 +265,7 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
   d.agent_mode = guard.keep.agent_mode;  // the tail kernel below runs outside the step's tick loop
   d.accum_rewards = guard.keep.accum_rewards;
   if (remi || aobs || areward || adone || h->ep.on) {
-    hipLaunchKernelGGL(k_agent_tail, dim3(grid_for((long)d.E * (2 * d.r + d.I), h->n_cu)), dim3(256), 0, st, d, remi, aobs,
+    hipLaunchKernelGGL(k_agent_tail, dim3(grid_for(h, (long)d.E * (2 * d.r + d.I))), dim3(256), 0, st, d, remi, aobs,
                        areward, adone, d.agent_first, h->ep);
     HIPCHK(hipGetLastError());
   }
