@@ -197,6 +197,66 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed);
  * generator yields archetypes[0], :174 - get row 0).  The buffer replaces the rows a tfx_set_poisson stream bound. */
 int tfx_set_spawn_archetypes(tfx_handle h, const uint8_t *dev, int32_t per_road, int32_t per_tick);
 
+/* Demand profiles on the device: arrivals that change over time (a rush hour, tidal flow), that weigh the entry roads
+ * (an arterial against side streets) and whose level differs from env to env of one batch, with no host work per
+ * decision.  This is a TRUE per-tick Poisson process - the car count of every tick is Poisson distributed and the ticks
+ * are independent - NOT the reference's generator, whose gaps between cars are round(Exp) whole ticks
+ * (traffic_env.py:160-164): that one stays tfx_set_poisson.  The rule is stateless: there is no stream position to
+ * freeze, clone or rebase, and the rows of any tick can be asked for at any time (tfx_demand_counts).
+ *
+ * A demand has K = n_profiles (1..16) profiles of S = n_segments (1..64) segments of seg_ticks >= 1 ticks each - the
+ * period is P = S * seg_ticks, which must fit an int32 - a tick_offset, and two HOST tables of uint32 thresholds
+ * (copied by the call; gym_traffic/devrng.py demand_tables builds them):
+ *   count_cdf[K][S][n_cdf], n_cdf in 1..256: count_cdf[k][s][c] = min(floor(P(N <= c) * 2^32), 0xFFFFFFFF) for
+ *     N ~ Poisson(mean[k][s]); the last entry is 0xFFFFFFFF: at most n_cdf - 1 cars per env per tick
+ *   road_cdf[K][S][n_entry]: the cumulative weights of the entry roads scaled the same way, the last entry 0xFFFFFFFF
+ * and profile_of_env, a DEVICE int32 [E] the caller owns: it is read when the arrivals are drawn, so it may be rewritten
+ * between calls (a curriculum, domain randomisation) with no re-capture; NULL: profile 0 everywhere.
+ *
+ * Rule 4.  For the tick whose device clock value is t, env `env` with stream id g (env + env_id_offset until a clone
+ * with TFX_CLONE_STREAM hands over its source's id):
+ *     k  = profile_of_env[env]                 (outside [0, K): the env gets no cars in this tick)
+ *     s  = floormod(t + tick_offset, P) / seg_ticks          (64-bit, floor modulo)
+ *     u  = philox4x32(ctr = {t, g, TAG_DCNT, 0}, key = seed)
+ *     N  = #{c in 0 .. n_cdf-2 : u0 >= count_cdf[k][s][c]}
+ *     car c (0 <= c < N):  w = word (c & 3) of philox4x32(ctr = {t, g, TAG_DROAD, c >> 2}, key = seed)
+ *                          ej = #{j in 0 .. n_entry-2 : w >= road_cdf[k][s][j]}
+ *     counts[env][ej] += 1
+ * with TAG_DCNT = 0x44434E54 and TAG_DROAD = 0x44524F44 (the other draws use 0x47415021, 0x524F4144, 0x41524348,
+ * 0x45504953 and 0x504F4F4C).  Comparisons and integer adds only: the device (k_demand, csrc/tfx_demand.hpp), the host
+ * mirror (devrng.demand_counts) and any sharding of the envs over handles agree to the bit.  Cars beyond what a road
+ * takes in a tick overflow, as with any count buffer.  The rule reads the handle's clock, like TFX_ACTION_CYCLE and
+ * TFX_SPAWN_PERIODIC: it is an input of the handle, nothing about it is reset by tfx_reset, tfx_reset_envs or an episode
+ * restart, and a clone on a handle whose clock differs follows that handle's clock.  An env that stands still in an
+ * agent step gets no cars for the ticks it skips - what a per-tick count buffer gives it.
+ *
+ * tfx_step and tfx_agent_step draw the rows of a call up front, in one launch (tfx_step: per chunk of the rows the
+ * handle's count buffer holds; a decision must fit it: 64 ticks, fewer beyond 32 MB of counts), and run from there on
+ * exactly as they do for a bound per-tick count buffer.
+ *
+ * tfx_set_demand replaces any earlier spawn rule, as tfx_set_poisson does; a later tfx_set_spawns / tfx_set_poisson /
+ * tfx_set_regular replaces it.  TFX_EINVAL, naming the field: a null struct or null tables, sizes out of range, a
+ * period that does not fit an int32, a table row that is not non-decreasing or does not end in 0xFFFFFFFF, no entry
+ * roads or more than 2048, a heterogeneous handle (archetype rows for this rule are not drawn yet).  TFX_ESTATE before
+ * tfx_bind_buffers.  A refused call changes nothing.
+ *
+ * tfx_clone_envs with TFX_CLONE_STREAM between two demand handles copies the stream id, so source and clone receive the
+ * same cars from then on (under the same profile_of_env entries, which are the caller's); it needs an equal seed, sizes,
+ * tick_offset and tables, else TFX_EINVAL, as it is between a demand handle and a Poisson or regular one. */
+typedef struct tfx_demand {
+  int32_t n_profiles, n_segments, seg_ticks, tick_offset, n_cdf;
+  const uint32_t *count_cdf, *road_cdf;   /* HOST */
+  const int32_t *profile_of_env;          /* DEVICE [E] or NULL */
+  uint64_t seed;
+} tfx_demand;
+int tfx_set_demand(tfx_handle h, const tfx_demand *dm);
+/* The rows rule 4 makes for clock ticks tick0 .. tick0 + n_ticks - 1, into the caller's device buffer int32
+ * [n_ticks][E][n_entry]: a preview for users (what will arrive in the next hour?) and the direct test handle on
+ * k_demand.  Read-only, one launch on `stream`, no host synchronisation; captured graphs stay valid and
+ * tfx_debug_fail_after does not count the launch.  TFX_EINVAL: a NULL handle, NULL `out`, a negative n_ticks;
+ * TFX_ESTATE before tfx_bind_buffers or without a demand. */
+int tfx_demand_counts(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *out, void *stream);
+
 /* TrafficEnv._step (traffic_env.py:224-248), n_ticks times: phase/elapsed update, spawns,
  * move_cars, advance_finished_cars | advance_hack, steps += 1. */
 int tfx_step(tfx_handle h, int32_t n_ticks, void *stream);

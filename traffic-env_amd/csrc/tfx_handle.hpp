@@ -15,6 +15,7 @@
 #include "tfx.h"
 #include "tfx_common.hpp"
 #include "tfx_misc.hpp"
+#include "tfx_demand.hpp"
 
 using namespace tfx;
 
@@ -130,6 +131,18 @@ struct tfx_handle_s {
   PoissonRows prow{};
   int n_arch = 1;              // rows of the archetype table (tfx_config.n_archetypes, at least 1)
   void *dev_ps = nullptr;      // counts | gap_left | draws | cdf [| seq | rows]
+  // demand profiles (tfx_set_demand, rule 4 of include/tfx.h; k_demand, tfx_demand.hpp): the rows of a call are drawn up
+  // front into a count buffer of the handle's own, which the move kernels read as a bound per-tick count buffer
+  bool demand = false;
+  DemandDev dm{};
+  int *dm_counts = nullptr;    // [demand_rows][E][n_entry]
+  int demand_rows = 1;         // ticks of arrival counts the buffer holds (tfx_step draws longer calls in chunks)
+  // counts | gap_left | draws (the stream words a clone with TFX_CLONE_STREAM copies: unused, as a Poisson handle
+  // owns them) | sid | count_cdf | road_cdf
+  void *dev_dm = nullptr;
+  int *dm_gap = nullptr;
+  unsigned *dm_draws = nullptr;
+  std::vector<uint32_t> dm_count_cdf, dm_road_cdf;  // the host copies (two handles must hold the same to share a stream)
   int *dev_greedy = nullptr;   // [E][I] actions
   // episodes on the device (tfx_set_episodes): the parameter block, and its copy on the device (k_res reads it through a pointer)
   EpDev ep{};

@@ -47,6 +47,15 @@ void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const v
              (void *)s.passed_dst, (void *)s.done_tick, (void *)s.n_trips, (void *)s.trip_times, s.trip_cap,
              (void *)s.greedy_act);
   }
+  // demand profiles (tfx_set_demand): k_demand's arguments - the tables' sizes, the seed, the caller's profile_of_env
+  // and the handle's own buffers (input_gen covers a buffer that lands on the address an earlier one had)
+  if (h->demand) {
+    const size_t used = strlen(key);
+    const DemandDev &m = h->dm;
+    snprintf(key + used, n - used, "|D%d.%d.%d.%d.%d.%u.%u|%p|%p|%p|%p|%p", m.K, m.S, m.seg_ticks, m.tick_offset, m.n_cdf,
+             m.seed_lo, m.seed_hi, (const void *)m.profile, (const void *)m.count_cdf, (const void *)m.road_cdf,
+             (const void *)m.sid, (const void *)h->dm_counts);
+  }
 }
 
 
@@ -97,6 +106,9 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
   if (h->action_per_tick)
     return fail(TFX_EINVAL, "the fused agent step holds ONE action for all its ticks (bind the action buffer "
                             "with per_tick = 0)");
+  if (h->demand && n_ticks > h->demand_rows)
+    return fail(TFX_EINVAL, "n_ticks = %d: a decision's arrivals are drawn up front and the demand's count buffer holds %d "
+                            "rows at this batch size", n_ticks, h->demand_rows);
   hipStream_t st = (hipStream_t)stream;
   if (!res_usable(h, n_ticks)) {
     if (int rc = size_grids(h, true, n_ticks)) return rc;
@@ -147,6 +159,21 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
       if (rc == TFX_OK) rc = ticks(chunk);
       h->d.spawn_stride = 0;
       if (rows) h->d.spawn_arch_stride = 0;
+      h->d.action = act0;
+      done += chunk;
+    }
+    return rc;
+  }
+  if (h->demand && n_ticks > 0) {
+    // demand profiles (tfx_set_demand) take the same slot: the rows of the call, in chunks of the rows the handle's
+    // count buffer holds, ONE launch each.  The clock a chunk's launch reads is the one the chunk before it left.
+    int rc = TFX_OK;
+    const int *const act0 = h->d.action;
+    for (int done = 0; done < n_ticks && rc == TFX_OK;) {
+      const int chunk = n_ticks - done < h->demand_rows ? n_ticks - done : h->demand_rows;
+      rc = launch_demand(h, 1, 0, chunk, h->dm_counts, st);
+      if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
+      if (rc == TFX_OK) rc = ticks(chunk);
       h->d.action = act0;
       done += chunk;
     }
@@ -407,6 +434,7 @@ int tfx_destroy(tfx_handle h) {
     (void)hipEventDestroy(h->split_stagger);
   }
   if (h->dev_ps) (void)hipFree(h->dev_ps);
+  if (h->dev_dm) (void)hipFree(h->dev_dm);
   if (h->dev_greedy) (void)hipFree(h->dev_greedy);
   if (h->dev_tables) (void)hipFree(h->dev_tables);
   if (h->dev_scratch) (void)hipFree(h->dev_scratch);
@@ -562,6 +590,26 @@ int init_stream_ids(tfx_handle h) {
   return TFX_OK;
 }
 
+// another spawn rule replaces the demand profiles (tfx_set_demand): its buffers go
+void drop_demand(tfx_handle h) {
+  if (!h->demand) return;
+  h->demand = false;
+  if (h->dev_dm) { (void)hipFree(h->dev_dm); h->dev_dm = nullptr; }
+  // nothing of the handle keeps pointing into the freed buffer: the stream ids and the count rows the move kernels read
+  // lived in it (a caller that fails after this leaves a handle without spawns)
+  h->ps_sid = nullptr;
+  h->d.spawn = nullptr;
+  h->d.spawn_stride = 0;
+  h->d.spawn_mode = TFX_SPAWN_NONE;
+  h->spawn_per_tick = 0;
+  h->dm = DemandDev{};
+  h->dm_counts = nullptr;
+  h->dm_gap = nullptr;
+  h->dm_draws = nullptr;
+  h->dm_count_cdf.clear();
+  h->dm_road_cdf.clear();
+}
+
 // the Poisson stream's archetype rows stop feeding the move kernels (its counts no longer do either, or another row
 // source takes over); rows bound through tfx_set_spawn_archetypes stay
 void unbind_stream_rows(tfx_handle h) {
@@ -583,6 +631,7 @@ int tfx_set_spawns(tfx_handle h, int32_t mode, const int32_t *dev, int32_t perio
   ++h->input_gen;
   h->poisson = false;
   unbind_stream_rows(h);
+  drop_demand(h);  // (its rows were bound as a count buffer of the handle's own: a failing call below leaves no spawns)
   if (mode == TFX_SPAWN_PERIODIC) {
     if (period < 1) return fail(TFX_EINVAL, "spawn period must be >= 1");
     d.spawn_period = period;
@@ -617,6 +666,7 @@ int tfx_set_poisson(tfx_handle h, double cars_per_tick, uint64_t seed, const uin
   Dev &d = h->d;
   if (d.n_entry < 1) return fail(TFX_EINVAL, "no entry roads");
   ++h->input_gen;
+  drop_demand(h);
   unbind_stream_rows(h);
   h->prow = PoissonRows{};
   if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
@@ -678,6 +728,7 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed) {
   d.spawn_arch_S = 0;
   d.spawn_arch_stride = 0;
   h->prow = PoissonRows{};
+  drop_demand(h);
   if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
   long rows = ((long)32 << 20) / ((long)d.E * d.n_entry * 4);
   h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));
@@ -707,12 +758,134 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed) {
   return TFX_OK;
 }
 
+int tfx_set_demand(tfx_handle h, const tfx_demand *dm) {
+  // (the arguments first, as tfx_road_cells checks them: each cause is named whatever state the handle is in)
+  if (!dm) return fail(TFX_EINVAL, "demand: dm is null");
+  if (!dm->count_cdf) return fail(TFX_EINVAL, "demand: count_cdf is null");
+  if (!dm->road_cdf) return fail(TFX_EINVAL, "demand: road_cdf is null");
+  const int K = dm->n_profiles, S = dm->n_segments, n_cdf = dm->n_cdf;
+  if (K < 1 || K > DEMAND_MAX_PROFILES) return fail(TFX_EINVAL, "demand: n_profiles %d is outside 1..%d", K, DEMAND_MAX_PROFILES);
+  if (S < 1 || S > DEMAND_MAX_SEGMENTS) return fail(TFX_EINVAL, "demand: n_segments %d is outside 1..%d", S, DEMAND_MAX_SEGMENTS);
+  if (dm->seg_ticks < 1) return fail(TFX_EINVAL, "demand: seg_ticks %d is below 1", dm->seg_ticks);
+  if (n_cdf < 1 || n_cdf > DEMAND_MAX_CDF) return fail(TFX_EINVAL, "demand: n_cdf %d is outside 1..%d", n_cdf, DEMAND_MAX_CDF);
+  if ((long long)S * dm->seg_ticks > 0x7fffffffLL)
+    return fail(TFX_EINVAL, "demand: the period n_segments * seg_ticks = %lld does not fit an int32", (long long)S * dm->seg_ticks);
+  // a table row: non-decreasing thresholds, the last one 0xFFFFFFFF (k_demand's binary search relies on the order)
+  auto bad_row = [](const uint32_t *row, int n) {
+    for (int c = 1; c < n; ++c)
+      if (row[c] < row[c - 1]) return c;
+    return row[n - 1] != 0xFFFFFFFFu ? n : 0;
+  };
+  for (int ks = 0; ks < K * S; ++ks)
+    if (const int c = bad_row(dm->count_cdf + (size_t)ks * n_cdf, n_cdf))
+      return fail(TFX_EINVAL, c < n_cdf ? "demand: count_cdf row (%d, %d) decreases at %d" : "demand: count_cdf row (%d, %d) does not end in 0xFFFFFFFF",
+                  ks / S, ks % S, c);
+  if (int rc = check_handle(h, false)) return rc;
+  Dev &d = h->d;
+  if (h->het)
+    return fail(TFX_EINVAL, "demand: heterogeneous handles (tfx_config.n_archetypes) are not supported - rule 4 draws no archetype rows");
+  if (d.n_entry < 1) return fail(TFX_EINVAL, "demand: no entry roads");
+  if (d.n_entry > DEMAND_MAX_ENTRY) return fail(TFX_EINVAL, "demand: more than %d entry roads", DEMAND_MAX_ENTRY);
+  const int ne = d.n_entry;
+  for (int ks = 0; ks < K * S; ++ks)
+    if (const int c = bad_row(dm->road_cdf + (size_t)ks * ne, ne))
+      return fail(TFX_EINVAL, c < ne ? "demand: road_cdf row (%d, %d) decreases at %d" : "demand: road_cdf row (%d, %d) does not end in 0xFFFFFFFF",
+                  ks / S, ks % S, c);
+  if (int rc = check_handle(h, true)) return rc;
+  // rows of E x n_entry counts the handle draws per launch (at most 64, at most ~32 MB), as tfx_set_poisson sizes them
+  long rows = ((long)32 << 20) / ((long)d.E * ne * 4);
+  rows = rows < 1 ? 1 : (rows > 64 ? 64 : rows);
+  const size_t n_counts = (size_t)rows * d.E * ne, n_cc = (size_t)K * S * n_cdf, n_rc = (size_t)K * S * ne;
+  const size_t bytes = (n_counts + 3 * (size_t)d.E + n_cc + n_rc) * 4;
+  // the new buffers first: a call that fails here has changed nothing
+  void *buf = nullptr;
+  if (hipMalloc(&buf, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TFX_ENOMEM, "demand: hipMalloc(%zu bytes) failed", bytes);
+  }
+  int *base = (int *)buf;
+  unsigned *sid = (unsigned *)(base + n_counts + 2 * (size_t)d.E);
+  unsigned *cc = sid + d.E, *rc_ = cc + n_cc;
+  std::vector<unsigned> ids((size_t)d.E);
+  for (int e = 0; e < d.E; ++e) ids[(size_t)e] = (unsigned)(e + d.env_off);  // (as init_stream_ids)
+  if (hipMemset(buf, 0, (n_counts + 2 * (size_t)d.E) * 4) != hipSuccess ||
+      hipMemcpy(sid, ids.data(), ids.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(cc, dm->count_cdf, n_cc * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(rc_, dm->road_cdf, n_rc * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    const hipError_t e = hipGetLastError();
+    (void)hipFree(buf);
+    return fail(TFX_EDEVICE, "demand: uploading the tables failed: %s", hipGetErrorString(e));
+  }
+  // it replaces any earlier spawn rule, as tfx_set_poisson does
+  ++h->input_gen;
+  drop_demand(h);
+  unbind_stream_rows(h);
+  h->prow = PoissonRows{};
+  if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
+  h->ps = PoissonDev{};
+  h->ps_rate = 0.0;
+  h->poisson = false;
+  h->dev_dm = buf;
+  h->dm_counts = base;
+  h->dm_gap = base + n_counts;
+  h->dm_draws = (unsigned *)(base + n_counts + d.E);
+  h->ps_sid = sid;
+  h->demand_rows = (int)rows;
+  h->dm_count_cdf.assign(dm->count_cdf, dm->count_cdf + n_cc);
+  h->dm_road_cdf.assign(dm->road_cdf, dm->road_cdf + n_rc);
+  DemandDev &m = h->dm;
+  m.count_cdf = cc;
+  m.road_cdf = rc_;
+  m.sid = sid;
+  m.profile = dm->profile_of_env;
+  m.K = K; m.S = S; m.seg_ticks = dm->seg_ticks; m.tick_offset = dm->tick_offset; m.n_cdf = n_cdf;
+  m.seed_lo = (unsigned)dm->seed;
+  m.seed_hi = (unsigned)(dm->seed >> 32);
+  // what the move kernels see: a bound per-tick count buffer
+  d.spawn = h->dm_counts;
+  d.spawn_stride = (long)d.E * ne;
+  d.spawn_mode = TFX_SPAWN_COUNTS;
+  h->spawn_per_tick = 1;
+  h->demand = true;
+  return TFX_OK;
+}
+
+int tfx_demand_counts(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *out, void *stream) {
+  if (!out) return fail(TFX_EINVAL, "demand: out is null");
+  if (n_ticks < 0) return fail(TFX_EINVAL, "demand: n_ticks %d is negative", n_ticks);
+  if (int rc = check_handle(h, true)) return rc;
+  if (!h->demand) return fail(TFX_ESTATE, "demand: tfx_set_demand has not been called (or another spawn rule replaced it)");
+  if (n_ticks == 0) return TFX_OK;
+  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
+  return launch_demand(h, 0, tick0, n_ticks, out, (hipStream_t)stream);
+}
+
 int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
   if (n_ticks < 0) return fail(TFX_EINVAL, "n_ticks < 0");
   hipStream_t st = (hipStream_t)stream;
   // envs that fit a compute unit's LDS: all the ticks of the call in one launch (tfx_resident.hpp)
   if (n_ticks > 0 && res_usable(h, n_ticks)) {
+    if (h->demand) {
+      // demand profiles: k_res reads the rows as a bound per-tick count buffer - drawn up front, chunk by chunk.  The
+      // draw stays outside the timed region (tfx_profile), as it does on the per-tick path: an entry per chunk.
+      const int *const act0 = h->d.action;
+      int rc = TFX_OK;
+      for (int done = 0; done < n_ticks && rc == TFX_OK;) {
+        const int chunk = n_ticks - done < h->demand_rows ? n_ticks - done : h->demand_rows;
+        rc = launch_demand(h, 1, 0, chunk, h->dm_counts, st);
+        TickTimer timer(h);
+        if (rc == TFX_OK) rc = timer.begin(st);
+        if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
+        if (rc == TFX_OK) rc = launch_res(h, chunk, st);
+        h->d.action = act0;
+        if (rc == TFX_OK) h->fused_ticks += chunk;
+        if (rc == TFX_OK) rc = timer.mid(st);
+        if (rc == TFX_OK) rc = timer.end(st, chunk);
+        done += chunk;
+      }
+      return rc;
+    }
     TickTimer timer(h);
     if (int rc = timer.begin(st)) return rc;
     if (int rc = launch_res(h, n_ticks, st)) return rc;
@@ -740,6 +913,9 @@ int tfx_move_cars(tfx_handle h, void *stream) {
   if (int rc = size_grids(h, false, 1)) return rc;
   if (int rc = launch_greedy(h, (hipStream_t)stream)) return rc;
   if (int rc = launch_inputs(h, (hipStream_t)stream)) return rc;
+  if (h->demand) {  // (the row of the tick the clock stands at)
+    if (int rc = launch_demand(h, 1, 0, 1, h->dm_counts, (hipStream_t)stream)) return rc;
+  }
   return (pairs_usable(h) && !single_tick_ts(h)) ? launch_move_tt(h, false, false, 0, (hipStream_t)stream) : launch_move(h, 0, (hipStream_t)stream);
 }
 
@@ -966,9 +1142,22 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
   o.same = dst == src ? 1 : 0;
   o.skipped = dst->clone_skipped;
   if (flags & TFX_CLONE_STREAM) {
-    if (!dst->poisson || !src->poisson)
-      return fail(TFX_EINVAL, "clone: TFX_CLONE_STREAM needs an on-device arrival stream (tfx_set_poisson / tfx_set_regular) "
-                              "in both handles");
+    if (dst->demand != src->demand)
+      return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (demand profiles in one handle only)");
+    if (dst->demand) {
+      // rule 4 has no position: the stream id alone makes source and clone receive the same cars - under the same
+      // seed, sizes, offset and tables (the host copies)
+      const DemandDev &p = dst->dm, &q = src->dm;
+      if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the demand seed");
+      if (p.K != q.K || p.S != q.S || p.seg_ticks != q.seg_ticks || p.n_cdf != q.n_cdf)
+        return fail(TFX_EINVAL, "clone: the handles differ in the demand sizes (n_profiles, n_segments, seg_ticks, n_cdf)");
+      if (p.tick_offset != q.tick_offset) return fail(TFX_EINVAL, "clone: the handles differ in the demand tick_offset");
+      if (dst->dm_count_cdf != src->dm_count_cdf || dst->dm_road_cdf != src->dm_road_cdf)
+        return fail(TFX_EINVAL, "clone: the handles differ in the demand tables (count_cdf / road_cdf)");
+    }
+    if (!dst->demand && (!dst->poisson || !src->poisson))
+      return fail(TFX_EINVAL, "clone: TFX_CLONE_STREAM needs an on-device arrival stream (tfx_set_poisson / tfx_set_regular / "
+                              "tfx_set_demand) in both handles");
     const PoissonDev &p = dst->ps, &q = src->ps;
     if (p.regular != q.regular) return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (poisson / regular)");
     if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the stream seed");
@@ -977,8 +1166,8 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
     if (p.burst != q.burst) return fail(TFX_EINVAL, "clone: the handles differ in the stream burst");
     // (the same kind of stream on the same archetype table: both draw rows, or neither does)
     o.stream = 1;
-    o.d_gap = p.gap_left; o.s_gap = q.gap_left;
-    o.d_draws = p.draws; o.s_draws = q.draws;
+    o.d_gap = dst->demand ? dst->dm_gap : p.gap_left; o.s_gap = src->demand ? src->dm_gap : q.gap_left;
+    o.d_draws = dst->demand ? dst->dm_draws : p.draws; o.s_draws = src->demand ? src->dm_draws : q.draws;
     o.d_sid = dst->ps_sid; o.s_sid = src->ps_sid;
     o.d_seq = dst->prow.seq; o.s_seq = src->prow.seq;
   }

@@ -171,6 +171,26 @@ int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
   return TFX_OK;
 }
 
+// Grid of k_demand (tfx_demand.hpp): a wavefront per (tick row, env) item, four to a workgroup; a few workgroups per
+// compute unit stride over more, as tile_grid's kernels do
+long demand_grid(const tfx_handle_s *h, int n_ticks) {
+  long grid = ((long)n_ticks * h->d.E + 3) / 4;
+  const long cap = (long)h->n_cu * 16;
+  if (grid > cap) grid = cap;
+  if (grid < 1) grid = 1;
+  return grid_capped(h, grid);
+}
+
+// Rule 4's rows for n_ticks clock ticks into `out` - from the device clock on (use_clock: the rows of a call about to
+// be enqueued on st) or from tick0 on (the preview).  One launch; it writes nothing but `out`.
+int launch_demand(tfx_handle h, int use_clock, int tick0, int n_ticks, int *out, hipStream_t st) {
+  const size_t lds = (size_t)4 * 2 * h->d.n_entry * sizeof(unsigned);
+  hipLaunchKernelGGL(k_demand, dim3((unsigned)demand_grid(h, n_ticks)), dim3(256), lds, st, h->d, h->dm, use_clock, tick0,
+                     n_ticks, out);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
 // Producers of the inputs of ONE tick when they are generated on the device tick by tick: the Poisson stream inside
 // agent steps and single launches (tfx_step generates whole calls up front, see there).  The greedy controller's
 // decisions are made by the advance of the tick before (advance_item); k_greedy runs once per call.

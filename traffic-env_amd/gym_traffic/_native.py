@@ -14,6 +14,7 @@ CLONE_STREAM, CLONE_EPISODE = 1, 2      # flags of tfx_clone_envs
 MEASURE_ACCUMULATE = 1                  # flag of tfx_road_measures
 CELLS_ACCUMULATE = 1                    # flag of tfx_road_cells
 MAX_CELLS = 32                          # TFX_MAX_CELLS
+DEMAND_MAX_PROFILES, DEMAND_MAX_SEGMENTS, DEMAND_MAX_CDF = 16, 64, 256   # limits of tfx_set_demand
 
 
 class TfxConfig(C.Structure):
@@ -49,6 +50,13 @@ class TfxCellBuffers(C.Structure):
     _fields_ = [("n_cars", C.c_void_p), ("speed_sum", C.c_void_p)]
 
 
+class TfxDemand(C.Structure):
+    _fields_ = [("n_profiles", C.c_int32), ("n_segments", C.c_int32), ("seg_ticks", C.c_int32),
+                ("tick_offset", C.c_int32), ("n_cdf", C.c_int32),
+                ("count_cdf", C.c_void_p), ("road_cdf", C.c_void_p), ("profile_of_env", C.c_void_p),
+                ("seed", C.c_uint64)]
+
+
 class TfxError(RuntimeError):
     pass
 
@@ -73,6 +81,8 @@ _PROTOS = {
     "tfx_set_poisson": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_void_p, C.c_int32]),
     "tfx_set_regular": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64]),
     "tfx_set_spawn_archetypes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "tfx_set_demand": (C.c_int, [C.c_void_p, C.POINTER(TfxDemand)]),
+    "tfx_demand_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "tfx_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "tfx_move_cars": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tfx_advance_finished_cars": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -212,6 +212,8 @@ class TfxEngine(object):
         # episodes on the device (set_episodes): None while off
         self.ep_return = self.ep_len = self.final_return = self.final_len = self.truncated = self.ep_index = None
         self.episode_pool = None    # the engine restarts clone from (set_episode_pool)
+        # demand profiles (set_demand): None while another spawn rule is bound
+        self.demand = self.demand_profile = self.demand_tables = None
         # views with the reference's attribute names (traffic_env.py:372-376)
         self.passed = self.obs[:, :r]
         self.detected = self.obs[:, r:2 * r]
@@ -506,6 +508,7 @@ class TfxEngine(object):
         cdf = gap_table(cars_per_tick)
         nat.check(self.lib.tfx_set_poisson(self.h, float(cars_per_tick), int(seed),
                                            cdf.ctypes.data_as(C.c_void_p), int(cdf.size)))
+        self.demand = self.demand_profile = self.demand_tables = None
         self._spawn_bound = None
         self._rows_buf, self._rows_key = None, None
 
@@ -516,8 +519,55 @@ class TfxEngine(object):
         import math
         every, burst = round(1 / cars_per_tick), math.ceil(cars_per_tick)
         nat.check(self.lib.tfx_set_regular(self.h, int(every), int(burst), int(seed)))
+        self.demand = self.demand_profile = self.demand_tables = None
         self._spawn_bound = None
         self._rows_buf, self._rows_key = None, None   # (heterogeneous cars: every car is row 0, traffic_env.py:174)
+
+    def set_demand(self, means, weights=None, seg_ticks=1, tick_offset=0, seed=0, profile_of_env=None, n_cdf=None):
+        """Demand profiles on the device (tfx_set_demand, rule 4 of include/tfx.h): a true per-tick Poisson process whose
+        mean changes over time, weighs the entry roads and differs from env to env.  means: [K][S] cars per env per tick
+        of profile k in segment s (K <= 16, S <= 64 segments of seg_ticks ticks; the clock tick t is in segment
+        floormod(t + tick_offset, S * seg_ticks) // seg_ticks); weights: [K][S][n_entry] (or [n_entry]) weights of the
+        entry roads in entry-index order, None: equal.  profile_of_env: int32 [E] device tensor, read whenever arrivals
+        are drawn - rewrite it between calls at will; None: one of zeros is made.  It is exposed as `demand_profile`, the
+        tables as `demand_tables` (devrng.demand_counts mirrors the rule from them).  Replaces any earlier spawn rule."""
+        from gym_traffic.devrng import demand_tables
+        tables = demand_tables(means, weights, n_cdf=n_cdf, n_entry=self.n_entry)
+        K, S, n = tables.count_cdf.shape
+        if profile_of_env is None:
+            profile_of_env = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
+        prof = profile_of_env
+        if not isinstance(prof, torch.Tensor) or prof.dtype != torch.int32 or tuple(prof.shape) != (self.E,) \
+                or not prof.is_cuda or not prof.is_contiguous():
+            raise ValueError("profile_of_env must be a contiguous int32 [%d] device tensor" % self.E)
+        cc = np.ascontiguousarray(tables.count_cdf, np.uint32)
+        rc = np.ascontiguousarray(tables.road_cdf, np.uint32)
+        dm = nat.TfxDemand()
+        dm.n_profiles, dm.n_segments, dm.seg_ticks, dm.tick_offset, dm.n_cdf = K, S, int(seg_ticks), int(tick_offset), n
+        dm.count_cdf, dm.road_cdf = cc.ctypes.data_as(C.c_void_p), rc.ctypes.data_as(C.c_void_p)
+        dm.profile_of_env = _ptr(prof)
+        dm.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_set_demand(self.h, C.byref(dm)))
+        self.demand_profile, self.demand_tables = prof, tables
+        self.demand = dict(seg_ticks=int(seg_ticks), tick_offset=int(tick_offset), seed=int(seed))
+        self._spawn_bound = None
+        self._rows_buf, self._rows_key = None, None
+
+    def demand_counts(self, tick0, n_ticks, out=None):
+        """int32 [n_ticks, E, n_entry] device tensor: the cars rule 4 gives every env on every entry road in clock ticks
+        tick0 .. tick0 + n_ticks - 1 under the demand_profile as it stands (tfx_demand_counts: one read-only launch, no
+        host synchronisation) - a preview of the demand, and what devrng.demand_counts computes on the host."""
+        shape = (int(n_ticks), self.E, self.n_entry)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("demand_counts(out=): a contiguous int32 [%d, %d, %d] device tensor" % shape)
+        if shape[0] == 0:
+            return out                  # (an empty tensor has no address to hand over)
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_demand_counts(self.h, int(tick0), int(n_ticks), _ptr(out), self._stream()))
+        return out
 
     def set_greedy(self, spacing=3):
         """On-device greedy controller (algorithms/greedy.py:14-16), a decision every `spacing` ticks."""
@@ -575,6 +625,7 @@ class TfxEngine(object):
         if period is not None:
             key = ("periodic", int(period))
             if self._spawn_bound != key:
+                self.demand = self.demand_profile = self.demand_tables = None
                 nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_PERIODIC, None, int(period), 0))
                 self._spawn_bound = key
         elif counts is not None:
@@ -590,9 +641,11 @@ class TfxEngine(object):
                 key = ("held", c.data_ptr())
             self._spawn_buf = c
             if self._spawn_bound != key:
+                self.demand = self.demand_profile = self.demand_tables = None
                 nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_COUNTS, _ptr(c), 0, 1 if per_tick else 0))
                 self._spawn_bound = key
         elif self._spawn_bound != ("none",):
+            self.demand = self.demand_profile = self.demand_tables = None
             nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_NONE, None, 0, 0))
             self._spawn_bound = ("none",)
 
@@ -667,6 +720,7 @@ class TfxEngine(object):
             self._action_bound = ka
         ks = ("per_tick" if per_tick else "held", c.data_ptr())
         if self._spawn_bound != ks:
+            self.demand = self.demand_profile = self.demand_tables = None
             nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_COUNTS, _ptr(c), 0, 1 if per_tick else 0))
             self._spawn_bound = ks
         self._action_buf, self._spawn_buf = a, c

@@ -16,7 +16,13 @@ and return the rows of each tick next to its counts.
 (tfx_set_episodes, rule 2 of include/tfx.h).  `clone_plan` and `road_measures` state two more device rules in NumPy: which
 envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per road.  `road_cells` does the same for
 tfx_road_cells (cars and speeds per cell of road); `cell_edges` makes the uniform edges that leave no car out.
+
+`demand_tables`, `demand_segment` and `demand_counts` belong to the demand profiles (tfx_set_demand, rule 4 of
+include/tfx.h): the threshold tables the device reads, the segment of a clock tick, and the rule itself in NumPy - a pure
+function of (seed, stream id, clock tick), with no state to carry: a true per-tick Poisson process, not the reference's
+rounded-gap generator that PoissonMirror mirrors.
 """
+import collections
 import math
 
 import numpy as np
@@ -26,6 +32,7 @@ W0, W1 = 0x9E3779B9, 0xBB67AE85
 TAG_GAP, TAG_ROAD, TAG_ARCH = 0x47415021, 0x524F4144, 0x41524348
 TAG_EPISODE = 0x45504953
 TAG_POOL = 0x504F4F4C
+TAG_DCNT, TAG_DROAD = 0x44434E54, 0x44524F44
 MASK = 0xFFFFFFFF
 
 
@@ -55,6 +62,21 @@ def philox4x32_first(c0, c1, c2, c3, k0, k1):
         k0 = (k0 + W0) & MASK
         k1 = (k1 + W1) & MASK
     return c0
+
+
+def philox4x32_words(c0, c1, c2, c3, k0, k1):
+    """All four output words of philox4x32 for arrays of counters (uint32 values in uint64 arrays, broadcast against
+    each other)."""
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, np.uint64) & np.uint64(MASK) for c in (c0, c1, c2, c3)])
+    m = np.uint64(MASK)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(M0) * c0
+        p1 = np.uint64(M1) * c2
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ np.uint64(k0)) & m, p1 & m, ((p0 >> s32) ^ c3 ^ np.uint64(k1)) & m, p0 & m
+        k0 = (k0 + W0) & MASK
+        k1 = (k1 + W1) & MASK
+    return c0, c1, c2, c3
 
 
 def episode_phases(seed, env_ids, ep_index, I):
@@ -342,3 +364,126 @@ class RegularMirror(object):
                 np.add.at(out[row], ((ur * np.uint64(self.n_entry)) >> np.uint64(32)).astype(np.int64), 1)
                 self.car[e] += self.burst
         return out if self.rows is None else (out, self.rows.tick(out, self.env_ids, draw=False))
+
+
+# ---- demand profiles (tfx_set_demand, rule 4 of include/tfx.h) ----------------------------------------------------------
+DemandTables = collections.namedtuple("DemandTables", "count_cdf road_cdf")
+DEMAND_MAX_CDF = 256
+
+
+def _poisson_cdf(mean, n):
+    """P(N <= c) for c = 0 .. n-1, N ~ Poisson(mean), in binary64 (the terms through logarithms: no overflow)."""
+    if mean == 0.0:
+        return np.ones(n)
+    c = np.arange(n, dtype=np.float64)
+    lg = np.array([math.lgamma(i + 1.0) for i in range(n)])
+    return np.minimum(np.cumsum(np.exp(c * math.log(mean) - mean - lg)), 1.0)
+
+
+def _thresholds(p):
+    """min(floor(p * 2^32), 0xFFFFFFFF) along the last axis, the last entry forced to 0xFFFFFFFF."""
+    t = np.minimum(np.floor(np.asarray(p, np.float64) * 4294967296.0), float(MASK)).astype(np.uint64)
+    t = np.maximum.accumulate(t, axis=-1)
+    t[..., -1] = MASK
+    return t.astype(np.uint32)
+
+
+def demand_tables(means, weights=None, n_cdf=None, n_entry=None, tail=1e-12):
+    """The two host tables of tfx_set_demand -> DemandTables(count_cdf uint32 [K, S, n_cdf], road_cdf uint32 [K, S, n_entry]).
+    means: [K][S] mean cars per env per tick of profile k in segment s (>= 0).  weights: [K][S][n_entry] (or [n_entry],
+    for every profile and segment) non-negative weights of the entry roads, in entry-index order; None: equal weights
+    (then n_entry is needed).  A road of weight zero receives no car.  n_cdf: entries per count row (at most n_cdf - 1
+    cars per env per tick); default: the smallest one that leaves less than `tail` of any row's mass beyond it, capped
+    at 256.  count_cdf[k][s][c] = min(floor(P(N <= c) * 2^32), 0xFFFFFFFF) for N ~ Poisson(means[k][s]); road_cdf holds the
+    cumulative weights scaled the same way; the last entry of every row is 0xFFFFFFFF."""
+    means = np.asarray(means, np.float64)
+    if means.ndim != 2 or means.size == 0 or not np.all(np.isfinite(means)) or (means < 0).any():
+        raise ValueError("means must be a [K][S] array of finite values >= 0")
+    K, S = means.shape
+    if weights is None:
+        if n_entry is None:
+            raise ValueError("equal weights need n_entry")
+        weights = np.ones(int(n_entry))
+    weights = np.asarray(weights, np.float64)
+    if weights.ndim == 1:
+        weights = np.broadcast_to(weights, (K, S, weights.shape[0]))
+    if weights.shape[:2] != (K, S) or weights.ndim != 3 or weights.shape[2] < 1:
+        raise ValueError("weights must be [K][S][n_entry] (or [n_entry])")
+    if n_entry is not None and weights.shape[2] != int(n_entry):
+        raise ValueError("weights hold %d entry roads, n_entry is %d" % (weights.shape[2], int(n_entry)))
+    if not np.all(np.isfinite(weights)) or (weights < 0).any() or (weights.sum(axis=-1) <= 0).any():
+        raise ValueError("weights must be finite, >= 0, and not all zero in any row")
+    if n_cdf is None:
+        n_cdf = 1
+        for mean in means.ravel():
+            cdf = _poisson_cdf(float(mean), DEMAND_MAX_CDF)
+            enough = np.nonzero(1.0 - cdf < tail)[0]
+            n_cdf = max(n_cdf, int(enough[0]) + 1 if enough.size else DEMAND_MAX_CDF)
+    n_cdf = int(n_cdf)
+    if not 1 <= n_cdf <= DEMAND_MAX_CDF:
+        raise ValueError("n_cdf must be in 1..%d" % DEMAND_MAX_CDF)
+    count = np.stack([np.stack([_poisson_cdf(float(means[k, s]), n_cdf) for s in range(S)]) for k in range(K)])
+    road = np.cumsum(weights, axis=-1) / weights.sum(axis=-1, keepdims=True)
+    return DemandTables(_thresholds(count), _thresholds(road))
+
+
+def _clock32(ticks):
+    """int64 array of the int32 clock values the ticks wrap to"""
+    t = np.asarray(ticks, np.int64)
+    return ((t + (1 << 31)) & MASK) - (1 << 31)
+
+
+def demand_segment(ticks, n_segments, seg_ticks=1, tick_offset=0):
+    """Segment of clock tick(s) t (rule 4): floormod(t + tick_offset, n_segments * seg_ticks) // seg_ticks, in 64 bits.
+    The device clock is an int32 that wraps: ticks outside the int32 range are wrapped into it first, as the device
+    does with `clock + row`."""
+    t = _clock32(ticks) + np.int64(tick_offset)
+    return (np.mod(t, np.int64(int(n_segments) * int(seg_ticks))) // np.int64(seg_ticks)).astype(np.int64)
+
+
+def demand_counts(seed, stream_ids, ticks, tables, profile_of_env=None, seg_ticks=1, tick_offset=0):
+    """Rule 4 of include/tfx.h in NumPy -> int32 [T, E, n_entry]: the cars env e (stream id stream_ids[e]: its global env
+    id, or its source's after a clone with its stream) receives on each entry road in clock tick ticks[t] (an int32 clock
+    value; anything else wraps to one, as the device clock does).  tables: a
+    DemandTables; profile_of_env: int [E] (None: profile 0; outside [0, K): no cars).  A pure function of its arguments:
+    any subset of envs or ticks, in any order, gives the same rows."""
+    count_cdf, road_cdf = [np.asarray(a, np.uint32).astype(np.uint64) for a in tables]
+    K, S, n_cdf = count_cdf.shape
+    ne = road_cdf.shape[2]
+    g = np.asarray(stream_ids, np.int64).reshape(-1) & MASK
+    t = _clock32(ticks).reshape(-1)
+    T, E = len(t), len(g)
+    prof = np.zeros(E, np.int64) if profile_of_env is None else np.asarray(profile_of_env, np.int64).reshape(-1)
+    if len(prof) != E:
+        raise ValueError("profile_of_env must hold one profile per env")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & MASK, seed >> 32
+    out = np.zeros((T, E, ne), np.int32)
+    if T == 0 or E == 0:
+        return out
+    valid = (prof >= 0) & (prof < K)
+    k = np.where(valid, prof, 0)
+    seg = demand_segment(t, S, seg_ticks, tick_offset)
+    tw = np.broadcast_to((t & MASK)[:, None], (T, E))
+    gw = np.broadcast_to(g[None, :], (T, E))
+    u0 = philox4x32_first(tw, gw, TAG_DCNT, 0, k0, k1)
+    rows = count_cdf[k[None, :], seg[:, None]]                       # [T, E, n_cdf]
+    N = (u0[..., None] >= rows[..., :n_cdf - 1]).sum(axis=-1)
+    N = np.where(valid[None, :], N, 0).reshape(-1)
+    if ne == 1:
+        out.reshape(-1)[:] = N
+        return out
+    item = np.repeat(np.arange(T * E), N)
+    if item.size == 0:
+        return out
+    c = np.arange(item.size) - np.repeat(np.cumsum(N) - N, N)      # car index within its item
+    flat = out.reshape(-1)
+    ks = (k[None, :] * S + seg[:, None]).reshape(-1)
+    road_rows = road_cdf.reshape(K * S, ne)
+    for lo in range(0, item.size, 1 << 18):
+        it, cc = item[lo:lo + (1 << 18)], c[lo:lo + (1 << 18)]
+        words = philox4x32_words(tw.reshape(-1)[it], gw.reshape(-1)[it], TAG_DROAD, cc >> 2, k0, k1)
+        w = np.choose(cc & 3, words)
+        ej = (w[:, None] >= road_rows[ks[it]][:, :ne - 1]).sum(axis=1)
+        flat += np.bincount(it * ne + ej, minlength=flat.size).astype(np.int32)
+    return out

@@ -7,7 +7,11 @@ generators (`spawn='poisson'|'regular'`: host RandomState schedules, bit-identic
 reference env seeded `seed + env_id`), from the on-device form of the reference's Poisson generator
 (`spawn='device'`: Philox streams keyed by (seed, global env id), no host work per tick - the one to
 use for throughput), from the on-device form of its `regular` generator (`spawn='regular_device'`: the reference's car
-counts per tick, entry roads from the same Philox streams) or from the on-device fixed-rate rule (`spawn='periodic'`).
+counts per tick, entry roads from the same Philox streams), from the on-device fixed-rate rule (`spawn='periodic'`) or
+from demand profiles on the device (`spawn='demand'`, rule 4 of include/tfx.h: a true per-tick Poisson process - not the
+reference's rounded-gap generator - whose mean changes over time, weighs the entry roads and differs from env to env:
+`demand=dict(means=[K][S], weights=[K][S][n_entry] or None, seg_ticks=, tick_offset=0)`, the profile of every env in the
+device tensor `demand_profile`, int32 [E], zeros at first and the user's to rewrite between calls).
 Sharding across GPUs is by env id (gym_traffic/distributed.py); envs share nothing.
 
 Mixed cars: `archetypes` takes the reference's `archetypes` table (traffic_env.py:35-43) as rows (v, l, a, delta, v0, b,
@@ -52,11 +56,13 @@ VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
 class TrafficVecEnv(object):
     def __init__(self, num_envs, m, n, length, capacity=20, rate=0.5, local_cars_per_sec=0.12,
                  spawn='poisson', spawn_period=8, entry_spec=0, learn_switch=False, validate=False,
-                 seed=0, env_id_offset=0, device=None, archetypes=None, autoreset=False, episode_len=None):
+                 seed=0, env_id_offset=0, device=None, archetypes=None, autoreset=False, episode_len=None, demand=None):
         """archetypes: None (the reference's single archetype) or float [n, 8] rows (v, l, a, delta, v0, b, T, s0) of
         the archetype table, n <= 64 - every spawn mode then makes mixed cars as the module docstring says.
         autoreset / episode_len: episodes on the device, see the module docstring (episode_len needs autoreset; in
-        validate mode the trip log of an ended episode stays readable until the next decision begins)."""
+        validate mode the trip log of an ended episode stays readable until the next decision begins).
+        demand: with spawn='demand', the keyword arguments of TfxEngine.set_demand other than the seed - means, weights,
+        seg_ticks, tick_offset, n_cdf (single-archetype envs only)."""
         if episode_len is not None and not autoreset:
             raise ValueError("episode_len needs autoreset=True (the time limit is kept on the device)")
         self.num_envs = int(num_envs)
@@ -64,7 +70,7 @@ class TrafficVecEnv(object):
         self._ctor = dict(m=m, n=n, length=length, capacity=capacity, rate=rate, local_cars_per_sec=local_cars_per_sec,
                           spawn=spawn, spawn_period=spawn_period, entry_spec=entry_spec, learn_switch=learn_switch,
                           validate=validate, seed=seed, env_id_offset=env_id_offset, device=device,
-                          archetypes=archetypes, autoreset=autoreset, episode_len=episode_len)
+                          archetypes=archetypes, autoreset=autoreset, episode_len=episode_len, demand=demand)
         self.graph = GridRoad(m, n, length)
         self.graph.generate_entrypoints(entry_spec)
         tab = None if archetypes is None else np.asarray(archetypes, np.float32).reshape(-1, 8)
@@ -94,12 +100,22 @@ class TrafficVecEnv(object):
             eng.set_poisson(self.cars_per_sec * self.rate, seed=seed)
         elif spawn == 'regular_device':
             eng.set_regular(self.cars_per_sec * self.rate, seed=seed)
+        elif spawn == 'demand':
+            if not isinstance(demand, dict) or "means" not in demand:
+                raise ValueError("spawn='demand' needs demand=dict(means=..., weights=..., seg_ticks=..., tick_offset=0)")
+            unknown = set(demand) - {"means", "weights", "seg_ticks", "tick_offset", "n_cdf"}
+            if unknown:
+                raise ValueError("demand: unknown keys %s" % sorted(unknown))
+            eng.set_demand(seed=seed, **demand)
+            self.demand_profile = eng.demand_profile
         elif spawn == 'periodic':
             eng.set_spawns(period=spawn_period)
         elif spawn in (None, 'none'):
             eng.set_spawns()
         else:
-            raise ValueError("spawn must be poisson|regular|device|regular_device|periodic|none")
+            raise ValueError("spawn must be poisson|regular|device|regular_device|demand|periodic|none")
+        if demand is not None and spawn != 'demand':
+            raise ValueError("demand= needs spawn='demand'")
         self._phase_rng = np.random.RandomState(seed + 7919 + self.env_id_offset)
         self.obs, self.rewards, self.done = eng.obs, eng.rewards, eng.done
         self.autoreset = bool(autoreset)
@@ -240,19 +256,29 @@ class TrafficVecEnv(object):
     def clone_envs(self, src_of_env, source=None, streams=True, episodes=True):
         """Env e becomes a copy of env src_of_env[e] of `source` (another TrafficVecEnv of the same world; default: this
         one); -1 leaves env e alone.  One device launch, no host synchronisation (TfxEngine.clone_envs).  streams: the
-        clone also continues its source's arrival stream - on the device for spawn='device' | 'regular_device', and for
+        clone also continues its source's arrival stream - on the device for spawn='device' | 'regular_device' | 'demand'
+        (a demand env also takes its source's demand_profile entry, gathered on the device from the index tensor), and for
         the host-replayed modes ('poisson' | 'regular') by copying the source envs' generator states, so env e replays
         what its source would have replayed; both envs must use the same spawn mode.  episodes: with autoreset on in
         both, the running episode's return / length / index travel too.  In place a source must not itself be
         overwritten (devrng.clone_plan); such envs are left alone and counted in engine.clone_skipped()."""
         other = self if source is None else source
         eng = self.engine
-        on_device = self.spawn in ('device', 'regular_device')
+        on_device = self.spawn in ('device', 'regular_device', 'demand')
         if streams and self.spawn != other.spawn:
             raise ValueError("clone_envs(streams=True) needs the same spawn mode in both envs (%r / %r)"
                              % (self.spawn, other.spawn))
         idx = eng.clone_envs(src_of_env, source=other.engine, streams=bool(streams and on_device),
                              episodes=bool(episodes and self.autoreset and other.autoreset))
+        if streams and self.spawn == 'demand':
+            # the envs the clone applied to (devrng.clone_plan's rule, on the device) take their sources' profiles
+            s = idx.long()
+            ok = (s >= 0) & (s < other.num_envs)
+            sc = s.clamp(0, other.num_envs - 1)
+            if other is self:
+                t = s[sc]
+                ok &= (t == -1) | (t == s)
+            self.demand_profile.copy_(torch.where(ok, other.demand_profile[sc], self.demand_profile))
         if streams and self.spawn in ('poisson', 'regular'):
             from gym_traffic.devrng import clone_plan
             host = idx.cpu().numpy()
