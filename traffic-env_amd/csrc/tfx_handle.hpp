@@ -16,6 +16,7 @@
 #include "tfx_common.hpp"
 #include "tfx_misc.hpp"
 #include "tfx_demand.hpp"
+#include "tfx_stream_layout.hpp"
 
 using namespace tfx;
 
@@ -52,6 +53,34 @@ struct CapturedSeq {
   const char *step_kernel = "";
 };
 enum { SEQ_AGENT = 0, SEQ_STEP = 1 };  // tfx_agent_step's decision, a tfx_step call of a launch-bound handle
+
+// The arrival stream a handle draws on the device (rules 1 and 4 of include/tfx.h) over its ONE device allocation
+// (stream_layout).  stage_stream builds it, install_stream binds it to the move kernels, drop_stream releases it
+// (tfx_hip.hip); the draws (launch_stream, k_res), tfx_clone_envs with TFX_CLONE_STREAM and stream_key consume it.
+enum StreamKind { STREAM_NONE, STREAM_POISSON, STREAM_REGULAR, STREAM_DEMAND };
+struct ArrivalStream {
+  StreamKind kind = STREAM_NONE;
+  void *buf = nullptr;
+  int *counts = nullptr;  // [rows][E][n_entry]: what the move kernels read as Dev::spawn
+  int rows = 1;
+  int *gap = nullptr;     // the stream words of the envs: a clone with TFX_CLONE_STREAM copies them
+  unsigned *draws = nullptr, *sid = nullptr;
+  unsigned *tables = nullptr;
+  // rule 1: k_poisson's and k_res's arguments, the archetype rows of heterogeneous cars (rows == nullptr: none drawn;
+  // bound as Dev::spawn_arch while d.spawn_arch == prow.rows), the rate the Poisson stream was set up with
+  PoissonDev ps{};
+  PoissonRows prow{};
+  double rate = 0.0;
+  // rule 4: k_demand's arguments, the host copies of its tables (two handles must hold the same to share a stream)
+  DemandDev dm{};
+  std::vector<uint32_t> count_cdf, road_cdf;
+  bool drawn() const { return kind != STREAM_NONE; }
+  // rule 4 is stateless: every caller draws the rows of its ticks up front, from the device clock on
+  bool upfront() const { return kind == STREAM_DEMAND; }
+  // rule 1 keeps a position per env: k_res draws inside its launch, tfx_step a call's rows up front, everything else
+  // tick by tick (draws_between_ticks, tfx_launch.hpp)
+  bool stateful() const { return kind == STREAM_POISSON || kind == STREAM_REGULAR; }
+};
 
 struct tfx_handle_s {
   tfx_config cfg;
@@ -121,39 +150,20 @@ struct tfx_handle_s {
   unsigned long long input_gen = 0;
   bool use_graph = true;  // TFX_GRAPH=0 disables
   int fail_after = 0;  // tfx_debug_fail_after: the n-th launch from now fails (error-path tests); 0 = off
-  // on-device Poisson arrivals / greedy controller (own buffers)
-  bool poisson = false, greedy = false;
+  // the arrival stream drawn on the device, if any (tfx_set_poisson / tfx_set_regular / tfx_set_demand)
+  ArrivalStream stream;
+  // greedy controller (own buffer)
+  bool greedy = false;
   int greedy_spacing = 3;
-  int poisson_rows = 1;        // ticks of arrival counts the Poisson buffer holds (tfx_step generates a call's worth up front)
-  PoissonDev ps{};
-  // heterogeneous cars: the Poisson stream's archetype rows (k_poisson<true>), in dev_ps after the cdf; rows == nullptr:
-  // no rows drawn (single archetype, the regular stream).  Bound as Dev::spawn_arch while d.spawn_arch == prow.rows
-  PoissonRows prow{};
   int n_arch = 1;              // rows of the archetype table (tfx_config.n_archetypes, at least 1)
-  void *dev_ps = nullptr;      // counts | gap_left | draws | cdf [| seq | rows]
-  // demand profiles (tfx_set_demand, rule 4 of include/tfx.h; k_demand, tfx_demand.hpp): the rows of a call are drawn up
-  // front into a count buffer of the handle's own, which the move kernels read as a bound per-tick count buffer
-  bool demand = false;
-  DemandDev dm{};
-  int *dm_counts = nullptr;    // [demand_rows][E][n_entry]
-  int demand_rows = 1;         // ticks of arrival counts the buffer holds (tfx_step draws longer calls in chunks)
-  // counts | gap_left | draws (the stream words a clone with TFX_CLONE_STREAM copies: unused, as a Poisson handle
-  // owns them) | sid | count_cdf | road_cdf
-  void *dev_dm = nullptr;
-  int *dm_gap = nullptr;
-  unsigned *dm_draws = nullptr;
-  std::vector<uint32_t> dm_count_cdf, dm_road_cdf;  // the host copies (two handles must hold the same to share a stream)
   int *dev_greedy = nullptr;   // [E][I] actions
   // episodes on the device (tfx_set_episodes): the parameter block, and its copy on the device (k_res reads it through a pointer)
   EpDev ep{};
   EpDev *dev_ep = nullptr;
   // warm restarts (tfx_set_episode_pool): the handle whose envs a restart clones, or null; the caller keeps it alive
   tfx_handle_s *pool = nullptr;
-  // tfx_clone_envs (tfx_clone.hpp): the device the handle lives on, the rate its Poisson stream was set up with (two
-  // handles must run the same stream to share one), the stream ids of its envs, the counter of envs left untouched
+  // tfx_clone_envs (tfx_clone.hpp): the device the handle lives on, the counter of envs left untouched
   int device = 0;
-  double ps_rate = 0.0;
-  unsigned *ps_sid = nullptr;
   unsigned long long *clone_skipped = nullptr;
   // tfx_road_measures (tfx_measure.hpp): TFX_MEASURE_GRID=n caps its launch at n workgroups (tests of its stride loop)
   int measure_grid = 0;

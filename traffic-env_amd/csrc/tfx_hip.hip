@@ -15,6 +15,7 @@
 // the cold kernels in tfx_misc.hpp.  tfx_step and tfx_agent_step read alike: size the grids, decide, run the body
 // (step_body / agent_sequence) on the caller's stream or replay its capture (run_captured).
 #include <cmath>
+#include <initializer_list>
 #include <new>
 
 #include "tfx_cells.hpp"
@@ -24,14 +25,23 @@
 
 namespace {
 
+// The arrival stream's part of that key: k_poisson's / k_res's and k_demand's arguments - the kind, the seeds, the tables'
+// sizes, the caller's profile_of_env and the stream's buffer
+void stream_key(const ArrivalStream &a, char *key, size_t n) {
+  const PoissonDev &p = a.ps;
+  const DemandDev &m = a.dm;
+  snprintf(key, n, "|S%d.%u.%u.%d.%d.%d.%d|D%d.%d.%d.%d.%d.%u.%u|%p|%p", (int)a.kind, p.seed_lo, p.seed_hi, p.n_cdf, p.regular,
+           p.every, p.burst, m.K, m.S, m.seg_ticks, m.tick_offset, m.n_cdf, m.seed_lo, m.seed_hi, (const void *)m.profile,
+           (const void *)a.buf);
+}
+
 // Everything a captured launch sequence bakes into its kernel arguments (a stale graph is never replayed, even when a
 // re-allocated buffer lands on the address the old one had: input_gen)
 void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const void *aobs, const void *areward,
                const void *adone) {
   const Dev &d = h->d;
-  snprintf(key, n, "%llu|%u|%u|%d.%d.%d.%d|%d%d%d|%ld|%d|%d|%p|%p|%p|%p|%d|%d|%ld|%p|%d|%d|%p|%p|%p|%p|%p|%p|%p|%p|%d.%d.%u.%u|%p|%p|%p|%p|%p|%p",
-           h->input_gen, h->ps.seed_lo, h->ps.seed_hi, h->ps.n_cdf, h->ps.regular, h->ps.every, h->ps.burst, (int)h->poisson,
-           (int)h->greedy, h->greedy_spacing, d.spawn_stride, n_ticks, remi, aobs, areward, adone, (const void *)d.action,
+  snprintf(key, n, "%llu|%d%d|%ld|%d|%d|%p|%p|%p|%p|%d|%d|%ld|%p|%d|%d|%p|%p|%p|%p|%p|%p|%p|%p|%d.%d.%u.%u|%p|%p|%p|%p|%p|%p",
+           h->input_gen, (int)h->greedy, h->greedy_spacing, d.spawn_stride, n_ticks, remi, aobs, areward, adone, (const void *)d.action,
            d.action_mode, d.action_period, d.action_stride, (const void *)d.spawn, d.spawn_mode, d.spawn_period, (void *)d.xv,
            (void *)d.w, (void *)d.obs, (void *)d.rewards, (void *)d.leading, (void *)d.lastcar, (void *)d.waiting,
            (void *)d.done_tick, h->ep.on, h->ep.max, h->ep.seed_lo, h->ep.seed_hi, (void *)h->ep.ep_return,
@@ -47,15 +57,8 @@ void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const v
              (void *)s.passed_dst, (void *)s.done_tick, (void *)s.n_trips, (void *)s.trip_times, s.trip_cap,
              (void *)s.greedy_act);
   }
-  // demand profiles (tfx_set_demand): k_demand's arguments - the tables' sizes, the seed, the caller's profile_of_env
-  // and the handle's own buffers (input_gen covers a buffer that lands on the address an earlier one had)
-  if (h->demand) {
-    const size_t used = strlen(key);
-    const DemandDev &m = h->dm;
-    snprintf(key + used, n - used, "|D%d.%d.%d.%d.%d.%u.%u|%p|%p|%p|%p|%p", m.K, m.S, m.seg_ticks, m.tick_offset, m.n_cdf,
-             m.seed_lo, m.seed_hi, (const void *)m.profile, (const void *)m.count_cdf, (const void *)m.road_cdf,
-             (const void *)m.sid, (const void *)h->dm_counts);
-  }
+  const size_t used = strlen(key);
+  stream_key(h->stream, key + used, n - used);
 }
 
 
@@ -106,9 +109,9 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
   if (h->action_per_tick)
     return fail(TFX_EINVAL, "the fused agent step holds ONE action for all its ticks (bind the action buffer "
                             "with per_tick = 0)");
-  if (h->demand && n_ticks > h->demand_rows)
+  if (h->stream.upfront() && n_ticks > h->stream.rows)
     return fail(TFX_EINVAL, "n_ticks = %d: a decision's arrivals are drawn up front and the demand's count buffer holds %d "
-                            "rows at this batch size", n_ticks, h->demand_rows);
+                            "rows at this batch size", n_ticks, h->stream.rows);
   hipStream_t st = (hipStream_t)stream;
   if (!res_usable(h, n_ticks)) {
     if (int rc = size_grids(h, true, n_ticks)) return rc;
@@ -130,6 +133,137 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
 
 namespace {
 
+// The handle's arrival stream goes: its rows stop feeding the move kernels - the counts, and the archetype rows it drew
+// (rows bound through tfx_set_spawn_archetypes stay) - and its buffer is freed.  Nothing of the handle keeps pointing
+// into it: a caller that fails after this leaves a handle without spawns.
+void drop_stream(tfx_handle h) {
+  ArrivalStream &s = h->stream;
+  if (!s.drawn()) return;
+  Dev &d = h->d;
+  if (d.spawn_arch && d.spawn_arch == s.prow.rows) {
+    d.spawn_arch = nullptr;
+    d.spawn_arch_S = 0;
+    d.spawn_arch_stride = 0;
+  }
+  d.spawn = nullptr;
+  d.spawn_stride = 0;
+  d.spawn_mode = TFX_SPAWN_NONE;
+  h->spawn_per_tick = 0;
+  (void)hipFree(s.buf);
+  s = ArrivalStream{};
+}
+
+// A new stream of `kind` for the handle's envs, staged WITHOUT touching the handle (a call that fails here has changed
+// nothing): the buffer (stream_layout), cleared - tick counters, car indices and seq start at 0, a Poisson stream's
+// gap at -1: first gap not drawn yet -, every env's stream keyed by its global id (tfx_clone_envs with
+// TFX_CLONE_STREAM copies ids), the kind's tables uploaded one behind the other.  The setter adds the kind's scalars.
+struct HostTable { const uint32_t *words; size_t n; };
+int stage_stream(tfx_handle h, StreamKind kind, uint64_t seed, std::initializer_list<HostTable> tables, ArrivalStream *out) {
+  const Dev &d = h->d;
+  const bool demand = kind == STREAM_DEMAND;
+  size_t n_tables = 0;
+  for (const HostTable &t : tables) n_tables += t.n;
+  // heterogeneous cars: the Poisson stream draws every car's archetype row (the regular stream's cars are row 0)
+  const int S = kind == STREAM_POISSON && h->het ? d.C - 2 : 0;
+  const StreamLayout l = stream_layout(d.E, d.n_entry, n_tables, S);
+  ArrivalStream s;
+  if (hipMalloc(&s.buf, l.bytes) != hipSuccess) {
+    const hipError_t e = hipGetLastError();
+    return demand ? fail(TFX_ENOMEM, "demand: hipMalloc(%zu bytes) failed", l.bytes)
+                  : fail(TFX_EDEVICE, "hipMalloc(arrival stream, %zu bytes): %s", l.bytes, hipGetErrorString(e));
+  }
+  char *base = (char *)s.buf;
+  s.kind = kind;
+  s.rows = l.rows;
+  s.counts = (int *)(base + l.counts);
+  s.gap = (int *)(base + l.gap);
+  s.draws = (unsigned *)(base + l.draws);
+  s.sid = (unsigned *)(base + l.sid);
+  s.tables = (unsigned *)(base + l.tables);
+  std::vector<unsigned> ids((size_t)d.E);
+  for (int e = 0; e < d.E; ++e) ids[(size_t)e] = (unsigned)(e + d.env_off);
+  bool ok = hipMemset(s.buf, 0, l.bytes) == hipSuccess &&
+            (kind != STREAM_POISSON || hipMemset(s.gap, 0xff, (size_t)d.E * 4) == hipSuccess) &&
+            hipMemcpy(s.sid, ids.data(), ids.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  unsigned *to = s.tables;
+  for (const HostTable &t : tables) {
+    ok = ok && hipMemcpy(to, t.words, t.n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    to += t.n;
+  }
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    (void)hipFree(s.buf);
+    return fail(TFX_EDEVICE, demand ? "demand: uploading the tables failed: %s" : "uploading the arrival stream failed: %s",
+                hipGetErrorString(e));
+  }
+  if (demand) {
+    s.dm.sid = s.sid;
+    s.dm.seed_lo = (unsigned)seed;
+    s.dm.seed_hi = (unsigned)(seed >> 32);
+  } else {
+    s.ps.counts = s.counts;
+    s.ps.gap_left = s.gap;
+    s.ps.draws = s.draws;
+    s.ps.sid = s.sid;
+    s.ps.seed_lo = (unsigned)seed;
+    s.ps.seed_hi = (unsigned)(seed >> 32);
+  }
+  if (S > 0) {
+    s.prow.seq = (unsigned *)(base + l.seq);
+    s.prow.rows = (uint8_t *)(base + l.arch);
+    s.prow.S = S;
+    s.prow.n_arch = h->n_arch;
+  }
+  *out = std::move(s);
+  return TFX_OK;
+}
+
+// The staged stream replaces whatever spawn rule the handle had.  What the move kernels see: a count buffer of the
+// handle's own - per tick for rule 4, whose callers draw their rows up front; one row for rule 1 (tfx_step's chunks set
+// the strides of theirs, for_stream_chunks) - and the stream's archetype rows or, where it draws none (every car of the
+// regular stream is archetypes[0], traffic_env.py:174), no rows at all.
+void install_stream(tfx_handle h, ArrivalStream &&s) {
+  Dev &d = h->d;
+  ++h->input_gen;
+  drop_stream(h);
+  h->stream = std::move(s);
+  const ArrivalStream &a = h->stream;
+  d.spawn = a.counts;
+  d.spawn_stride = a.upfront() ? (long)d.E * d.n_entry : 0;
+  d.spawn_mode = TFX_SPAWN_COUNTS;
+  h->spawn_per_tick = a.upfront() ? 1 : 0;
+  d.spawn_arch = a.prow.rows;
+  d.spawn_arch_S = a.prow.S;
+  d.spawn_arch_stride = 0;
+}
+
+// The ticks of a call under an arrival stream whose rows are drawn up front: in chunks of the rows the count buffer
+// holds, ONE launch each (they depend on nothing but the stream and, rule 4, the clock the chunk before left; a launch
+// per tick was the longest one of a cfg4 tick), then body(chunk).  A chunk's kernels count ticks from 0 - row t of the
+// count buffer, and of the stream's archetype rows (heterogeneous cars), is the chunk's tick t; a per-tick ACTION buffer
+// is indexed by the tick of the whole call, so its base moves along with the chunks.  Everything is put back on exit.
+template <class Body>
+int for_stream_chunks(tfx_handle h, int n_ticks, hipStream_t st, Body body) {
+  Dev &d = h->d;
+  const ArrivalStream &s = h->stream;
+  const int *const act0 = d.action;
+  const long stride0 = d.spawn_stride, arch_stride0 = d.spawn_arch_stride;
+  const bool rows = s.prow.rows && d.spawn_arch == s.prow.rows;
+  int rc = TFX_OK;
+  for (int done = 0; done < n_ticks && rc == TFX_OK; done += s.rows) {
+    const int chunk = n_ticks - done < s.rows ? n_ticks - done : s.rows;
+    rc = launch_stream(h, chunk, st);
+    d.spawn_stride = (long)d.E * d.n_entry;
+    if (rows) d.spawn_arch_stride = d.spawn_stride * s.prow.S;
+    if (act0 && h->action_per_tick) d.action = act0 + (size_t)done * d.action_stride;
+    if (rc == TFX_OK) rc = body(chunk);
+    d.spawn_stride = stride0;
+    d.spawn_arch_stride = arch_stride0;
+    d.action = act0;
+  }
+  return rc;
+}
+
 // the launches of a tfx_step call on the per-tick kernels, on `st`
 int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
   // a call's ticks, or one chunk of them: two halves on two streams where that pays (a chunk that splits is not captured)
@@ -141,45 +275,7 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
     return run_ticks(h, n, st, false, split);
   };
   if (int rc = launch_greedy(h, st)) return rc;  // (the decision of the call's first tick; later ones: advance_item)
-  if (h->poisson && n_ticks > 0) {
-    // the arrivals of the whole call (in chunks of the rows the count buffer holds) in ONE launch each: they depend
-    // on nothing but the stream, and a launch per tick was the longest one of a cfg4 tick
-    int rc = TFX_OK;
-    // a chunk's kernels count ticks from 0 (row t of the count buffer is the chunk's tick t); a per-tick ACTION buffer is
-    // indexed by the tick of the whole call, so its base moves along with the chunks
-    const int *const act0 = h->d.action;
-    // the stream's archetype rows (heterogeneous cars) follow its counts row for row
-    const bool rows = h->prow.rows && h->d.spawn_arch == h->prow.rows;
-    for (int done = 0; done < n_ticks && rc == TFX_OK;) {
-      const int chunk = n_ticks - done < h->poisson_rows ? n_ticks - done : h->poisson_rows;
-      rc = launch_poisson(h, chunk, st);
-      h->d.spawn_stride = (long)h->d.E * h->d.n_entry;
-      if (rows) h->d.spawn_arch_stride = (long)h->d.E * h->d.n_entry * h->prow.S;
-      if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
-      if (rc == TFX_OK) rc = ticks(chunk);
-      h->d.spawn_stride = 0;
-      if (rows) h->d.spawn_arch_stride = 0;
-      h->d.action = act0;
-      done += chunk;
-    }
-    return rc;
-  }
-  if (h->demand && n_ticks > 0) {
-    // demand profiles (tfx_set_demand) take the same slot: the rows of the call, in chunks of the rows the handle's
-    // count buffer holds, ONE launch each.  The clock a chunk's launch reads is the one the chunk before it left.
-    int rc = TFX_OK;
-    const int *const act0 = h->d.action;
-    for (int done = 0; done < n_ticks && rc == TFX_OK;) {
-      const int chunk = n_ticks - done < h->demand_rows ? n_ticks - done : h->demand_rows;
-      rc = launch_demand(h, 1, 0, chunk, h->dm_counts, st);
-      if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
-      if (rc == TFX_OK) rc = ticks(chunk);
-      h->d.action = act0;
-      done += chunk;
-    }
-    return rc;
-  }
-  return ticks(n_ticks);
+  return h->stream.drawn() && n_ticks > 0 ? for_stream_chunks(h, n_ticks, st, ticks) : ticks(n_ticks);
 }
 
 }  // namespace
@@ -433,8 +529,7 @@ int tfx_destroy(tfx_handle h) {
     (void)hipEventDestroy(h->split_join);
     (void)hipEventDestroy(h->split_stagger);
   }
-  if (h->dev_ps) (void)hipFree(h->dev_ps);
-  if (h->dev_dm) (void)hipFree(h->dev_dm);
+  drop_stream(h);
   if (h->dev_greedy) (void)hipFree(h->dev_greedy);
   if (h->dev_tables) (void)hipFree(h->dev_tables);
   if (h->dev_scratch) (void)hipFree(h->dev_scratch);
@@ -578,60 +673,11 @@ int tfx_set_actions(tfx_handle h, int32_t mode, const int32_t *dev, int32_t peri
   return TFX_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// every env's arrival stream starts out keyed by its global id (tfx_clone_envs with TFX_CLONE_STREAM copies ids)
-int init_stream_ids(tfx_handle h) {
-  std::vector<unsigned> ids((size_t)h->d.E);
-  for (int e = 0; e < h->d.E; ++e) ids[(size_t)e] = (unsigned)(e + h->d.env_off);
-  HIPCHK(hipMemcpy(h->ps_sid, ids.data(), ids.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-  return TFX_OK;
-}
-
-// another spawn rule replaces the demand profiles (tfx_set_demand): its buffers go
-void drop_demand(tfx_handle h) {
-  if (!h->demand) return;
-  h->demand = false;
-  if (h->dev_dm) { (void)hipFree(h->dev_dm); h->dev_dm = nullptr; }
-  // nothing of the handle keeps pointing into the freed buffer: the stream ids and the count rows the move kernels read
-  // lived in it (a caller that fails after this leaves a handle without spawns)
-  h->ps_sid = nullptr;
-  h->d.spawn = nullptr;
-  h->d.spawn_stride = 0;
-  h->d.spawn_mode = TFX_SPAWN_NONE;
-  h->spawn_per_tick = 0;
-  h->dm = DemandDev{};
-  h->dm_counts = nullptr;
-  h->dm_gap = nullptr;
-  h->dm_draws = nullptr;
-  h->dm_count_cdf.clear();
-  h->dm_road_cdf.clear();
-}
-
-// the Poisson stream's archetype rows stop feeding the move kernels (its counts no longer do either, or another row
-// source takes over); rows bound through tfx_set_spawn_archetypes stay
-void unbind_stream_rows(tfx_handle h) {
-  Dev &d = h->d;
-  if (d.spawn_arch && d.spawn_arch == h->prow.rows) {
-    d.spawn_arch = nullptr;
-    d.spawn_arch_S = 0;
-    d.spawn_arch_stride = 0;
-  }
-}
-
-}  // namespace
-
-extern "C" {
-
 int tfx_set_spawns(tfx_handle h, int32_t mode, const int32_t *dev, int32_t period, int32_t per_tick) {
   if (int rc = check_handle(h, false)) return rc;
   Dev &d = h->d;
   ++h->input_gen;
-  h->poisson = false;
-  unbind_stream_rows(h);
-  drop_demand(h);  // (its rows were bound as a count buffer of the handle's own: a failing call below leaves no spawns)
+  drop_stream(h);  // (its rows were bound as a count buffer of the handle's own: a failing call below leaves no spawns)
   if (mode == TFX_SPAWN_PERIODIC) {
     if (period < 1) return fail(TFX_EINVAL, "spawn period must be >= 1");
     d.spawn_period = period;
@@ -665,55 +711,12 @@ int tfx_set_poisson(tfx_handle h, double cars_per_tick, uint64_t seed, const uin
   if (!cdf || n_cdf < 1 || n_cdf > 65536) return fail(TFX_EINVAL, "gap table missing or too long");
   Dev &d = h->d;
   if (d.n_entry < 1) return fail(TFX_EINVAL, "no entry roads");
-  ++h->input_gen;
-  drop_demand(h);
-  unbind_stream_rows(h);
-  h->prow = PoissonRows{};
-  if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
-  // rows of E x n_entry counts: tfx_step generates that many ticks per launch (at most 64, at most ~32 MB)
-  long rows = ((long)32 << 20) / ((long)d.E * d.n_entry * 4);
-  // heterogeneous cars: and E x n_entry x S archetype rows per tick within ~64 MB (cfg2: 17 MB per tick)
-  const int S = d.C - 2;
-  if (h->het) {
-    const long arows = ((long)64 << 20) / ((long)d.E * d.n_entry * S);
-    if (arows < rows) rows = arows;
-  }
-  h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));
-  const size_t n_counts = (size_t)h->poisson_rows * d.E * d.n_entry;
-  const size_t n_seq = h->het ? (size_t)d.E * d.n_entry : 0;
-  const size_t bytes = (n_counts + 3 * (size_t)d.E + (size_t)n_cdf + n_seq) * 4 +
-                       (h->het ? (size_t)h->poisson_rows * d.E * d.n_entry * S : 0);
-  HIPCHK(hipMalloc(&h->dev_ps, bytes));
-  HIPCHK(hipMemset(h->dev_ps, 0, bytes));  // (seq starts at 0)
-  int *base = (int *)h->dev_ps;
-  h->ps_sid = (unsigned *)(base + n_counts + 2 * (size_t)d.E + n_cdf);
-  if (int rc = init_stream_ids(h)) return rc;
-  h->ps_rate = cars_per_tick;
-  if (h->het) {
-    h->prow.seq = h->ps_sid + d.E;
-    h->prow.rows = (uint8_t *)(h->prow.seq + n_seq);
-    h->prow.S = S;
-    h->prow.n_arch = h->n_arch;
-    d.spawn_arch = h->prow.rows;
-    d.spawn_arch_S = S;
-    d.spawn_arch_stride = 0;  // (tfx_step's chunks: E x n_entry x S, next to spawn_stride)
-  }
-  h->ps.counts = base;
-  h->ps.gap_left = base + n_counts;
-  h->ps.draws = (unsigned *)(base + n_counts + d.E);
-  h->ps.cdf = (const unsigned *)(base + n_counts + 2 * (size_t)d.E);
-  h->ps.sid = h->ps_sid;
-  h->ps.n_cdf = n_cdf;
-  h->ps.regular = h->ps.every = h->ps.burst = 0;
-  h->ps.seed_lo = (unsigned)seed;
-  h->ps.seed_hi = (unsigned)(seed >> 32);
-  HIPCHK(hipMemset(h->ps.gap_left, 0xff, (size_t)d.E * 4));  // -1: first gap not drawn yet
-  HIPCHK(hipMemcpy((void *)h->ps.cdf, cdf, (size_t)n_cdf * 4, hipMemcpyHostToDevice));
-  d.spawn = h->ps.counts;
-  d.spawn_stride = 0;
-  d.spawn_mode = TFX_SPAWN_COUNTS;
-  h->spawn_per_tick = 0;
-  h->poisson = true;
+  ArrivalStream s;
+  if (int rc = stage_stream(h, STREAM_POISSON, seed, {{cdf, (size_t)n_cdf}}, &s)) return rc;
+  s.ps.cdf = s.tables;
+  s.ps.n_cdf = n_cdf;
+  s.rate = cars_per_tick;
+  install_stream(h, std::move(s));
   return TFX_OK;
 }
 
@@ -722,39 +725,12 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed) {
   if (every < 0 || burst < 1) return fail(TFX_EINVAL, "every must be >= 0 and burst >= 1");
   Dev &d = h->d;
   if (d.n_entry < 1) return fail(TFX_EINVAL, "no entry roads");
-  ++h->input_gen;
-  // heterogeneous cars: every car of this stream is archetypes[0] (traffic_env.py:174) - no row buffer stays bound
-  d.spawn_arch = nullptr;
-  d.spawn_arch_S = 0;
-  d.spawn_arch_stride = 0;
-  h->prow = PoissonRows{};
-  drop_demand(h);
-  if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
-  long rows = ((long)32 << 20) / ((long)d.E * d.n_entry * 4);
-  h->poisson_rows = (int)(rows < 1 ? 1 : (rows > 64 ? 64 : rows));
-  const size_t n_counts = (size_t)h->poisson_rows * d.E * d.n_entry;
-  const size_t bytes = (n_counts + 3 * (size_t)d.E) * 4;
-  HIPCHK(hipMalloc(&h->dev_ps, bytes));
-  HIPCHK(hipMemset(h->dev_ps, 0, bytes));  // (tick counters and car indices start at 0)
-  int *base = (int *)h->dev_ps;
-  h->ps_sid = (unsigned *)(base + n_counts + 2 * (size_t)d.E);
-  if (int rc = init_stream_ids(h)) return rc;
-  h->ps_rate = 0.0;
-  h->ps = PoissonDev{};
-  h->ps.sid = h->ps_sid;
-  h->ps.counts = base;
-  h->ps.gap_left = base + n_counts;
-  h->ps.draws = (unsigned *)(base + n_counts + d.E);
-  h->ps.seed_lo = (unsigned)seed;
-  h->ps.seed_hi = (unsigned)(seed >> 32);
-  h->ps.regular = 1;
-  h->ps.every = every;
-  h->ps.burst = burst;
-  d.spawn = h->ps.counts;
-  d.spawn_stride = 0;
-  d.spawn_mode = TFX_SPAWN_COUNTS;
-  h->spawn_per_tick = 0;
-  h->poisson = true;  // (an arrival stream drawn on the device: every path of tfx_set_poisson serves it)
+  ArrivalStream s;
+  if (int rc = stage_stream(h, STREAM_REGULAR, seed, {}, &s)) return rc;
+  s.ps.regular = 1;
+  s.ps.every = every;
+  s.ps.burst = burst;
+  install_stream(h, std::move(s));
   return TFX_OK;
 }
 
@@ -792,61 +768,17 @@ int tfx_set_demand(tfx_handle h, const tfx_demand *dm) {
       return fail(TFX_EINVAL, c < ne ? "demand: road_cdf row (%d, %d) decreases at %d" : "demand: road_cdf row (%d, %d) does not end in 0xFFFFFFFF",
                   ks / S, ks % S, c);
   if (int rc = check_handle(h, true)) return rc;
-  // rows of E x n_entry counts the handle draws per launch (at most 64, at most ~32 MB), as tfx_set_poisson sizes them
-  long rows = ((long)32 << 20) / ((long)d.E * ne * 4);
-  rows = rows < 1 ? 1 : (rows > 64 ? 64 : rows);
-  const size_t n_counts = (size_t)rows * d.E * ne, n_cc = (size_t)K * S * n_cdf, n_rc = (size_t)K * S * ne;
-  const size_t bytes = (n_counts + 3 * (size_t)d.E + n_cc + n_rc) * 4;
-  // the new buffers first: a call that fails here has changed nothing
-  void *buf = nullptr;
-  if (hipMalloc(&buf, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(TFX_ENOMEM, "demand: hipMalloc(%zu bytes) failed", bytes);
-  }
-  int *base = (int *)buf;
-  unsigned *sid = (unsigned *)(base + n_counts + 2 * (size_t)d.E);
-  unsigned *cc = sid + d.E, *rc_ = cc + n_cc;
-  std::vector<unsigned> ids((size_t)d.E);
-  for (int e = 0; e < d.E; ++e) ids[(size_t)e] = (unsigned)(e + d.env_off);  // (as init_stream_ids)
-  if (hipMemset(buf, 0, (n_counts + 2 * (size_t)d.E) * 4) != hipSuccess ||
-      hipMemcpy(sid, ids.data(), ids.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(cc, dm->count_cdf, n_cc * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(rc_, dm->road_cdf, n_rc * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    const hipError_t e = hipGetLastError();
-    (void)hipFree(buf);
-    return fail(TFX_EDEVICE, "demand: uploading the tables failed: %s", hipGetErrorString(e));
-  }
-  // it replaces any earlier spawn rule, as tfx_set_poisson does
-  ++h->input_gen;
-  drop_demand(h);
-  unbind_stream_rows(h);
-  h->prow = PoissonRows{};
-  if (h->dev_ps) { (void)hipFree(h->dev_ps); h->dev_ps = nullptr; }
-  h->ps = PoissonDev{};
-  h->ps_rate = 0.0;
-  h->poisson = false;
-  h->dev_dm = buf;
-  h->dm_counts = base;
-  h->dm_gap = base + n_counts;
-  h->dm_draws = (unsigned *)(base + n_counts + d.E);
-  h->ps_sid = sid;
-  h->demand_rows = (int)rows;
-  h->dm_count_cdf.assign(dm->count_cdf, dm->count_cdf + n_cc);
-  h->dm_road_cdf.assign(dm->road_cdf, dm->road_cdf + n_rc);
-  DemandDev &m = h->dm;
-  m.count_cdf = cc;
-  m.road_cdf = rc_;
-  m.sid = sid;
+  const size_t n_cc = (size_t)K * S * n_cdf, n_rc = (size_t)K * S * ne;
+  ArrivalStream s;
+  if (int rc = stage_stream(h, STREAM_DEMAND, dm->seed, {{dm->count_cdf, n_cc}, {dm->road_cdf, n_rc}}, &s)) return rc;
+  s.count_cdf.assign(dm->count_cdf, dm->count_cdf + n_cc);
+  s.road_cdf.assign(dm->road_cdf, dm->road_cdf + n_rc);
+  DemandDev &m = s.dm;
+  m.count_cdf = s.tables;
+  m.road_cdf = s.tables + n_cc;
   m.profile = dm->profile_of_env;
   m.K = K; m.S = S; m.seg_ticks = dm->seg_ticks; m.tick_offset = dm->tick_offset; m.n_cdf = n_cdf;
-  m.seed_lo = (unsigned)dm->seed;
-  m.seed_hi = (unsigned)(dm->seed >> 32);
-  // what the move kernels see: a bound per-tick count buffer
-  d.spawn = h->dm_counts;
-  d.spawn_stride = (long)d.E * ne;
-  d.spawn_mode = TFX_SPAWN_COUNTS;
-  h->spawn_per_tick = 1;
-  h->demand = true;
+  install_stream(h, std::move(s));
   return TFX_OK;
 }
 
@@ -854,7 +786,7 @@ int tfx_demand_counts(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *out
   if (!out) return fail(TFX_EINVAL, "demand: out is null");
   if (n_ticks < 0) return fail(TFX_EINVAL, "demand: n_ticks %d is negative", n_ticks);
   if (int rc = check_handle(h, true)) return rc;
-  if (!h->demand) return fail(TFX_ESTATE, "demand: tfx_set_demand has not been called (or another spawn rule replaced it)");
+  if (!h->stream.upfront()) return fail(TFX_ESTATE, "demand: tfx_set_demand has not been called (or another spawn rule replaced it)");
   if (n_ticks == 0) return TFX_OK;
   // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
   return launch_demand(h, 0, tick0, n_ticks, out, (hipStream_t)stream);
@@ -866,32 +798,18 @@ int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   // envs that fit a compute unit's LDS: all the ticks of the call in one launch (tfx_resident.hpp)
   if (n_ticks > 0 && res_usable(h, n_ticks)) {
-    if (h->demand) {
-      // demand profiles: k_res reads the rows as a bound per-tick count buffer - drawn up front, chunk by chunk.  The
-      // draw stays outside the timed region (tfx_profile), as it does on the per-tick path: an entry per chunk.
-      const int *const act0 = h->d.action;
-      int rc = TFX_OK;
-      for (int done = 0; done < n_ticks && rc == TFX_OK;) {
-        const int chunk = n_ticks - done < h->demand_rows ? n_ticks - done : h->demand_rows;
-        rc = launch_demand(h, 1, 0, chunk, h->dm_counts, st);
-        TickTimer timer(h);
-        if (rc == TFX_OK) rc = timer.begin(st);
-        if (act0 && h->action_per_tick) h->d.action = act0 + (size_t)done * h->d.action_stride;
-        if (rc == TFX_OK) rc = launch_res(h, chunk, st);
-        h->d.action = act0;
-        if (rc == TFX_OK) h->fused_ticks += chunk;
-        if (rc == TFX_OK) rc = timer.mid(st);
-        if (rc == TFX_OK) rc = timer.end(st, chunk);
-        done += chunk;
-      }
-      return rc;
-    }
-    TickTimer timer(h);
-    if (int rc = timer.begin(st)) return rc;
-    if (int rc = launch_res(h, n_ticks, st)) return rc;
-    h->fused_ticks += n_ticks;
-    if (int rc = timer.mid(st)) return rc;
-    return timer.end(st, n_ticks);
+    auto fused = [&](int n) {
+      TickTimer timer(h);
+      if (int rc = timer.begin(st)) return rc;
+      if (int rc = launch_res(h, n, st)) return rc;
+      h->fused_ticks += n;
+      if (int rc = timer.mid(st)) return rc;
+      return timer.end(st, n);
+    };
+    // demand profiles: k_res reads the rows as a bound per-tick count buffer - drawn up front, chunk by chunk.  The draw
+    // stays outside the timed region (tfx_profile), as it does on the per-tick path: an entry per chunk.  (Rule 1: k_res
+    // draws inside its launch.)
+    return h->stream.upfront() ? for_stream_chunks(h, n_ticks, st, fused) : fused(n_ticks);
   }
   if (int rc = size_grids(h, false, n_ticks)) return rc;
   // Launch-bound handles (a few thousand tiles: cfg4 x 16, a 16x16 grid x 256 envs) replay the call's launches as a HIP
@@ -912,10 +830,8 @@ int tfx_move_cars(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
   if (int rc = size_grids(h, false, 1)) return rc;
   if (int rc = launch_greedy(h, (hipStream_t)stream)) return rc;
-  if (int rc = launch_inputs(h, (hipStream_t)stream)) return rc;
-  if (h->demand) {  // (the row of the tick the clock stands at)
-    if (int rc = launch_demand(h, 1, 0, 1, h->dm_counts, (hipStream_t)stream)) return rc;
-  }
+  // (rule 4: the row of the tick the clock stands at)
+  if (int rc = h->stream.upfront() ? launch_stream(h, 1, (hipStream_t)stream) : launch_inputs(h, (hipStream_t)stream)) return rc;
   return (pairs_usable(h) && !single_tick_ts(h)) ? launch_move_tt(h, false, false, 0, (hipStream_t)stream) : launch_move(h, 0, (hipStream_t)stream);
 }
 
@@ -1126,6 +1042,36 @@ int same_world(tfx_handle dst, tfx_handle src, const char *what) {
   return TFX_OK;
 }
 
+// Two handles whose envs can follow each other's arrival streams (TFX_CLONE_STREAM): the same kind of stream under the
+// same parameters (and, same_world, on the same archetype table: both draw rows, or neither does)
+int streams_compatible(tfx_handle dst, tfx_handle src) {
+  const ArrivalStream &a = dst->stream, &b = src->stream;
+  if (a.upfront() != b.upfront())
+    return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (demand profiles in one handle only)");
+  if (a.upfront()) {
+    // rule 4 has no position: the stream id alone makes source and clone receive the same cars - under the same
+    // seed, sizes, offset and tables (the host copies)
+    const DemandDev &p = a.dm, &q = b.dm;
+    if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the demand seed");
+    if (p.K != q.K || p.S != q.S || p.seg_ticks != q.seg_ticks || p.n_cdf != q.n_cdf)
+      return fail(TFX_EINVAL, "clone: the handles differ in the demand sizes (n_profiles, n_segments, seg_ticks, n_cdf)");
+    if (p.tick_offset != q.tick_offset) return fail(TFX_EINVAL, "clone: the handles differ in the demand tick_offset");
+    if (a.count_cdf != b.count_cdf || a.road_cdf != b.road_cdf)
+      return fail(TFX_EINVAL, "clone: the handles differ in the demand tables (count_cdf / road_cdf)");
+    return TFX_OK;
+  }
+  if (!a.drawn() || !b.drawn())
+    return fail(TFX_EINVAL, "clone: TFX_CLONE_STREAM needs an on-device arrival stream (tfx_set_poisson / tfx_set_regular / "
+                            "tfx_set_demand) in both handles");
+  const PoissonDev &p = a.ps, &q = b.ps;
+  if (p.regular != q.regular) return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (poisson / regular)");
+  if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the stream seed");
+  if (p.regular ? (p.every != q.every) : (a.rate != b.rate || p.n_cdf != q.n_cdf))
+    return fail(TFX_EINVAL, "clone: the handles differ in the stream rate");
+  if (p.burst != q.burst) return fail(TFX_EINVAL, "clone: the handles differ in the stream burst");
+  return TFX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1142,34 +1088,13 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
   o.same = dst == src ? 1 : 0;
   o.skipped = dst->clone_skipped;
   if (flags & TFX_CLONE_STREAM) {
-    if (dst->demand != src->demand)
-      return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (demand profiles in one handle only)");
-    if (dst->demand) {
-      // rule 4 has no position: the stream id alone makes source and clone receive the same cars - under the same
-      // seed, sizes, offset and tables (the host copies)
-      const DemandDev &p = dst->dm, &q = src->dm;
-      if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the demand seed");
-      if (p.K != q.K || p.S != q.S || p.seg_ticks != q.seg_ticks || p.n_cdf != q.n_cdf)
-        return fail(TFX_EINVAL, "clone: the handles differ in the demand sizes (n_profiles, n_segments, seg_ticks, n_cdf)");
-      if (p.tick_offset != q.tick_offset) return fail(TFX_EINVAL, "clone: the handles differ in the demand tick_offset");
-      if (dst->dm_count_cdf != src->dm_count_cdf || dst->dm_road_cdf != src->dm_road_cdf)
-        return fail(TFX_EINVAL, "clone: the handles differ in the demand tables (count_cdf / road_cdf)");
-    }
-    if (!dst->demand && (!dst->poisson || !src->poisson))
-      return fail(TFX_EINVAL, "clone: TFX_CLONE_STREAM needs an on-device arrival stream (tfx_set_poisson / tfx_set_regular / "
-                              "tfx_set_demand) in both handles");
-    const PoissonDev &p = dst->ps, &q = src->ps;
-    if (p.regular != q.regular) return fail(TFX_EINVAL, "clone: the handles differ in the stream kind (poisson / regular)");
-    if (p.seed_lo != q.seed_lo || p.seed_hi != q.seed_hi) return fail(TFX_EINVAL, "clone: the handles differ in the stream seed");
-    if (p.regular ? (p.every != q.every) : (dst->ps_rate != src->ps_rate || p.n_cdf != q.n_cdf))
-      return fail(TFX_EINVAL, "clone: the handles differ in the stream rate");
-    if (p.burst != q.burst) return fail(TFX_EINVAL, "clone: the handles differ in the stream burst");
-    // (the same kind of stream on the same archetype table: both draw rows, or neither does)
+    if (int rc = streams_compatible(dst, src)) return rc;
+    const ArrivalStream &p = dst->stream, &q = src->stream;
     o.stream = 1;
-    o.d_gap = dst->demand ? dst->dm_gap : p.gap_left; o.s_gap = src->demand ? src->dm_gap : q.gap_left;
-    o.d_draws = dst->demand ? dst->dm_draws : p.draws; o.s_draws = src->demand ? src->dm_draws : q.draws;
-    o.d_sid = dst->ps_sid; o.s_sid = src->ps_sid;
-    o.d_seq = dst->prow.seq; o.s_seq = src->prow.seq;
+    o.d_gap = p.gap; o.s_gap = q.gap;
+    o.d_draws = p.draws; o.s_draws = q.draws;
+    o.d_sid = p.sid; o.s_sid = q.sid;
+    o.d_seq = p.prow.seq; o.s_seq = q.prow.seq;
   }
   if (flags & TFX_CLONE_EPISODE) {
     if (dst->ep.on != src->ep.on)

@@ -161,12 +161,13 @@ int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
   const Dev &d = h->d;
   const int threads = d.E <= 64 ? 1024 : (d.E <= 1024 ? 256 : 64);
   const int pg = (int)grid_capped(h, d.E < h->n_cu * 16 ? d.E : h->n_cu * 16);
-  if (h->prow.rows)  // (heterogeneous cars: the archetype row of every car too, and a running count per entry road)
-    hipLaunchKernelGGL(k_poisson<true>, dim3(pg), dim3(threads), ((size_t)2 * d.n_entry + 2) * sizeof(int), st, d, h->ps,
-                       n_ticks, h->prow);
+  const ArrivalStream &s = h->stream;
+  if (s.prow.rows)  // (heterogeneous cars: the archetype row of every car too, and a running count per entry road)
+    hipLaunchKernelGGL(k_poisson<true>, dim3(pg), dim3(threads), ((size_t)2 * d.n_entry + 2) * sizeof(int), st, d, s.ps,
+                       n_ticks, s.prow);
   else
-    hipLaunchKernelGGL(k_poisson<false>, dim3(pg), dim3(threads), ((size_t)d.n_entry + 2) * sizeof(int), st, d, h->ps,
-                       n_ticks, h->prow);
+    hipLaunchKernelGGL(k_poisson<false>, dim3(pg), dim3(threads), ((size_t)d.n_entry + 2) * sizeof(int), st, d, s.ps,
+                       n_ticks, s.prow);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
@@ -185,18 +186,26 @@ long demand_grid(const tfx_handle_s *h, int n_ticks) {
 // be enqueued on st) or from tick0 on (the preview).  One launch; it writes nothing but `out`.
 int launch_demand(tfx_handle h, int use_clock, int tick0, int n_ticks, int *out, hipStream_t st) {
   const size_t lds = (size_t)4 * 2 * h->d.n_entry * sizeof(unsigned);
-  hipLaunchKernelGGL(k_demand, dim3((unsigned)demand_grid(h, n_ticks)), dim3(256), lds, st, h->d, h->dm, use_clock, tick0,
-                     n_ticks, out);
+  hipLaunchKernelGGL(k_demand, dim3((unsigned)demand_grid(h, n_ticks)), dim3(256), lds, st, h->d, h->stream.dm, use_clock,
+                     tick0, n_ticks, out);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
+
+// The stream's next n_rows rows into its count buffer, in one launch: rule 4 from the device clock on
+int launch_stream(tfx_handle h, int n_rows, hipStream_t st) {
+  return h->stream.upfront() ? launch_demand(h, 1, 0, n_rows, h->stream.counts, st) : launch_poisson(h, n_rows, st);
+}
+
+// The arrivals of a tick are produced by a launch between the ticks: a stream with a position, outside tfx_step's
+// chunks - those hold rows drawn up front, which the move kernels are told by a spawn_stride of a row (for_stream_chunks)
+bool draws_between_ticks(const tfx_handle_s *h) { return h->stream.stateful() && h->d.spawn_stride == 0; }
 
 // Producers of the inputs of ONE tick when they are generated on the device tick by tick: the Poisson stream inside
 // agent steps and single launches (tfx_step generates whole calls up front, see there).  The greedy controller's
 // decisions are made by the advance of the tick before (advance_item); k_greedy runs once per call.
 int launch_inputs(tfx_handle h, hipStream_t st) {
-  if (h->poisson && h->d.spawn_stride == 0) return launch_poisson(h, 1, st);
-  return TFX_OK;
+  return draws_between_ticks(h) ? launch_stream(h, 1, st) : TFX_OK;
 }
 
 int launch_greedy(tfx_handle h, hipStream_t st) {
@@ -323,8 +332,8 @@ int launch_res(tfx_handle h, int n_ticks, hipStream_t st, int tail = 0, int remi
   a.aobs = aobs;
   a.areward = areward;
   a.adone = adone;
-  a.poisson = h->poisson ? 1 : 0;
-  a.ps = h->ps;
+  a.poisson = h->stream.stateful() ? 1 : 0;
+  a.ps = h->stream.ps;
   a.epb = h->res_epb;
   a.n_ticks = n_ticks;
   a.greedy_spacing = h->greedy ? h->greedy_spacing : 0;
@@ -520,7 +529,7 @@ Dev sub_dev(const tfx_handle_s *h, int lo, int n, int *clock) {
 // (The greedy controller decides inside the advance.)
 constexpr size_t TAIL_LDS_MAX = (size_t)160 * 1024;
 bool tail_usable(tfx_handle h, bool upfront = false) {
-  if (!h->tail || (h->poisson && h->d.spawn_stride == 0 && !upfront) || h->d.layout != 1) return false;
+  if (!h->tail || (draws_between_ticks(h) && !upfront) || h->d.layout != 1) return false;
   if (tail_lds_bytes(h->d.R, h->d.I, h->het) > TAIL_LDS_MAX) return false;
   // (the halves of a split call - chosen for the whole range, split_usable - keep k_tail whatever their own size)
   return h->tail == 2 || h->d.E >= h->n_cu || h->split_half >= 0;
@@ -534,7 +543,7 @@ bool tail_usable(tfx_handle h, bool upfront = false) {
 bool split_usable(tfx_handle h, int n_ticks, bool agent = false) {
   if (!h->split || h->prof || n_ticks < 2 || !pairs_usable(h, n_ticks) || !tail_usable(h)) return false;
   if (h->d.E < 2) return false;
-  if (agent && (res_usable(h, n_ticks) || h->poisson)) return false;
+  if (agent && (res_usable(h, n_ticks) || h->stream.stateful())) return false;
   if (h->split == 2) return true;
   // (round 4, us per tick, two halves / one range: 288 envs 61.7 / 47.6, 320 52.3 / 52.5, 352 63.6 / 52.4, 384 56.8 / 62.3,
   // 448 60.9 / 66.3, 512 64.3 / 71.4, 768 84.8 / 93.4: from three quarters of an env per CU and half on)

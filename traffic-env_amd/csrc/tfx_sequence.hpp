@@ -248,11 +248,11 @@ int agent_sequence(tfx_handle h, int n_ticks, int remi, float *aobs, float *arew
       HIPCHK(hipGetLastError());
     }
   }
-  if (h->demand) {
+  if (h->stream.upfront()) {
     // demand profiles (tfx_set_demand): the decision's rows up front, from the device clock on - exact because rule 4
     // is stateless: an env that overflows simply does not consume the rows of the ticks it skips.  From here on the
     // decision runs as it does for a bound per-tick count buffer.
-    if (int rc = launch_demand(h, 1, 0, n_ticks, h->dm_counts, st)) return rc;
+    if (int rc = launch_stream(h, n_ticks, st)) return rc;
   }
   if (res_usable(h, n_ticks)) {
     // every tick of the decision AND its tail (remi, observation, rewards, done flags) in one launch
