@@ -559,6 +559,64 @@ int tfx_road_cells(tfx_handle h, const float *edges, int32_t n_cells, const tfx_
                    void *stream);
 /* Test support: the launch geometry tfx_road_cells uses for this handle and n_cells - workgroups, and wavefronts. */
 int tfx_cells_launch(tfx_handle h, int32_t n_cells, int32_t *grid, int32_t *waves);
+/* Top-view frames on the device: chosen envs of the batch drawn as RGBA images - the picture TrafficEnv.render() gives of
+ * one env, and the vehicle-position image signal-control agents read - from one read-only pass over the live cars of
+ * those envs (k_frames, csrc/tfx_frames.hpp).  The cost follows the envs drawn, not the batch; without this call the
+ * route is tfx_export_ring of every ring slot of every env and a host loop over the cars.
+ *
+ * Definition, as a function of the image tfx_export_ring would produce at that moment (on a ring-layout handle: of xv
+ * itself), of leading / lastcar and of the light words inside obs - so it is defined in every state a handle can be in,
+ * as the measures are.  It is integer geometry; the only float step is one float32 multiply per car end.
+ *   size      px = S pixels per road length, TFX_FRAME_PX_MIN <= S <= TFX_FRAME_PX_MAX.  A frame is H x W pixels of 4
+ *             bytes R, G, B, A; W = (n + 1) * S + 1, H = (m + 1) * S + 1 (tfx_frame_size).  The image row is the grid's
+ *             row coordinate (row 0 at the top); intersection (row, col) has its centre at pixel (cx, cy) =
+ *             ((col + 1) * S, (row + 1) * S), (column, row) of the image.
+ *   roads     every road is one pixel wide and lies one pixel beside the centre line, on the side where
+ *             GridRoad._unit_segments (roadgraph.py) puts its eps.  With t the pixel along the road from its start, the
+ *             train road of direction block d into intersection (row, col) has its pixel t at
+ *               d = 0: (cx - S + t, cy - 1)    d = 1: (cx + S - t, cy + 1)
+ *               d = 2: (cx + 1, cy - S + t)    d = 3: (cx - 1, cy + S - t)
+ *             An exit road continues the road it follows, away from the grid, from the centre of that road's
+ *             intersection on: the four exit blocks, in _unit_segments' order, continue d = 3 out of row 0 ((cx - 1,
+ *             cy - t)), d = 0 out of the last column ((cx + t, cy - 1)), d = 2 out of the last row ((cx + 1, cy + t)) and
+ *             d = 1 out of column 0 ((cx - t, cy + 1)).
+ *   owned     a road owns the pixels t = 2 .. S - 2 only, S - 3 of them: it stays out of the 3 x 3 box round each
+ *             intersection.  No two roads share a pixel and every owned pixel lies inside the frame.
+ *   colours   every byte outside a road's own pixels is 0xFF (white, alpha 255).  A road's own pixels take its light's
+ *             colour (update_colors, traffic_env.py:335-346; gym_traffic.render.light_colours): with phase(e) = 1 for d <
+ *             2, else 0, and the words current_phase / elapsed of the road's intersection, yellow (255,255,0) iff phase(e)
+ *             == current_phase and elapsed < yellow_ticks; red (255,0,0) iff phase(e) == current_phase and not so fresh,
+ *             or the other phase and fresh; green (0,255,0) otherwise, and on every exit road.  Alpha is 255.
+ *   cars      take road e's cars from the head, as the measures do.  A car's length l is that of the archetype row it
+ *             carries (a single-archetype handle: car_l).  With k = float32(S - 3) / float32(length), computed once on
+ *             the host, a car whose x is NaN is not drawn; otherwise
+ *               a = clamp(floorf(x * k), 0, S - 4)    b = clamp(floorf((x - l) * k), 0, S - 4)
+ *             clamped in float before the conversion, and the car turns pixels t = 2 + b .. 2 + a of its road blue
+ *             (0,0,255).  Neither expression has a form a compiler could contract; the clamp makes the rule total: x >
+ *             length (between tfx_move_cars and the advance), x - l < 0, infinities.
+ * Every pixel has one writer and one value: the device stores each road pixel once, with its final value.
+ *
+ * env_ids: device int32 [n_frames], frame f shows env env_ids[f]; NULL: envs 0 .. n_frames - 1 (then n_frames <= E).
+ * An id outside [0, E) is no error: that frame is all background, nothing is read for it.  An env may appear in several
+ * frames.  out: device memory, [n_frames][H][W][4] bytes.  TFX_FRAMES_ROADS_ONLY: the background is not written, only the
+ * road pixels are - the caller promises that `out` holds the background of an earlier call with the same px (a video
+ * logger that reuses one tensor); a frame whose id is out of range then has its road pixels written white.
+ *
+ * At most one memset (the background) and one launch on `stream`, no host synchronisation; nothing in the handle or in
+ * the caller's bound state is written: captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not
+ * count the launch.  TFX_MEASURE_GRID and TFX_GRID_CAP cap the launch as they cap the cells'.  The arguments are checked
+ * before the handle.  TFX_EINVAL: NULL `out`, n_frames < 1, px outside TFX_FRAME_PX_MIN .. TFX_FRAME_PX_MAX, unknown
+ * flag bits, a NULL handle, n_frames > E with env_ids NULL, a frame of 2^31 pixels or more; TFX_ESTATE before
+ * tfx_bind_buffers.  gym_traffic/devrng.py frames states the definition in NumPy, frame_geometry the roads' pixels. */
+#define TFX_FRAME_PX_MIN 8
+#define TFX_FRAME_PX_MAX 256
+enum { TFX_FRAMES_ROADS_ONLY = 1 };
+int tfx_frame_size(tfx_handle h, int32_t px, int32_t *height, int32_t *width);
+int tfx_frames(tfx_handle h, const int32_t *env_ids, int32_t n_frames, int32_t px, uint8_t *out, int32_t flags,
+               void *stream);
+/* Test support: the launch geometry tfx_frames uses for this handle, n_frames and px - workgroups, and wavefronts (one
+ * per (frame, tile) item at a time). */
+int tfx_frames_launch(tfx_handle h, int32_t n_frames, int32_t px, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

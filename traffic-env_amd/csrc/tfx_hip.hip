@@ -19,6 +19,7 @@
 #include <new>
 
 #include "tfx_cells.hpp"
+#include "tfx_frames.hpp"
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
 #include "tfx_sequence.hpp"
@@ -1214,6 +1215,63 @@ int tfx_cells_launch(tfx_handle h, int32_t n_cells, int32_t *grid, int32_t *wave
   if (n_cells < 1 || n_cells > TFX_MAX_CELLS)
     return fail(TFX_EINVAL, "cells: n_cells %d is outside 1..%d", n_cells, TFX_MAX_CELLS);
   const long g = tile_grid(h, true);
+  if (grid) *grid = (int32_t)g;
+  if (waves) *waves = (int32_t)(g * 4);
+  return TFX_OK;
+}
+
+// the px of the three frame calls
+static int frame_px_ok(int32_t px) {
+  if (px < TFX_FRAME_PX_MIN || px > TFX_FRAME_PX_MAX)
+    return fail(TFX_EINVAL, "frames: px %d is outside %d..%d", px, TFX_FRAME_PX_MIN, TFX_FRAME_PX_MAX);
+  return TFX_OK;
+}
+
+int tfx_frame_size(tfx_handle h, int32_t px, int32_t *height, int32_t *width) {
+  if (int rc = frame_px_ok(px)) return rc;
+  if (int rc = check_handle(h, false)) return rc;
+  if (height) *height = (h->cfg.m + 1) * px + 1;
+  if (width) *width = (h->cfg.n + 1) * px + 1;
+  return TFX_OK;
+}
+
+int tfx_frames(tfx_handle h, const int32_t *env_ids, int32_t n_frames, int32_t px, uint8_t *out, int32_t flags,
+               void *stream) {
+  // (the arguments first, as tfx_road_cells checks them: each cause is named whatever state the handle is in)
+  if (!out) return fail(TFX_EINVAL, "frames: out is null");
+  if (n_frames < 1) return fail(TFX_EINVAL, "frames: n_frames %d is less than 1", n_frames);
+  if (int rc = frame_px_ok(px)) return rc;
+  if (flags & ~TFX_FRAMES_ROADS_ONLY) return fail(TFX_EINVAL, "unknown frame flags 0x%x", flags);
+  if (int rc = check_handle(h, false)) return rc;
+  if (!env_ids && n_frames > h->d.E)
+    return fail(TFX_EINVAL, "frames: n_frames %d is more than the handle's %d envs and env_ids is null", n_frames, h->d.E);
+  const long long W = (long long)(h->cfg.n + 1) * px + 1, H = (long long)(h->cfg.m + 1) * px + 1;
+  if (W * H > 0x7fffffffll) return fail(TFX_EINVAL, "frames: a frame of %lld x %lld pixels is too large", H, W);
+  if (int rc = check_handle(h, true)) return rc;
+  FrameArgs f{};
+  f.env_ids = env_ids;
+  f.out = reinterpret_cast<unsigned *>(out);
+  f.n_frames = n_frames;
+  f.roads_only = (flags & TFX_FRAMES_ROADS_ONLY) ? 1 : 0;
+  f.m = h->cfg.m;
+  f.n = h->cfg.n;
+  f.S = px;
+  f.W = (int)W;
+  f.H = (int)H;
+  f.k = (float)(px - 3) / h->cfg.length;  // one float32 division, on the host
+  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
+  if (!(flags & TFX_FRAMES_ROADS_ONLY))
+    HIPCHK(hipMemsetAsync(out, 0xFF, (size_t)n_frames * (size_t)(W * H) * 4, (hipStream_t)stream));
+  hipLaunchKernelGGL(k_frames, dim3((unsigned)tile_grid(h, true, n_frames)), dim3(256), 0, (hipStream_t)stream, h->d, f);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_frames_launch(tfx_handle h, int32_t n_frames, int32_t px, int32_t *grid, int32_t *waves) {
+  if (n_frames < 1) return fail(TFX_EINVAL, "frames: n_frames %d is less than 1", n_frames);
+  if (int rc = frame_px_ok(px)) return rc;
+  if (int rc = check_handle(h, false)) return rc;
+  const long g = tile_grid(h, true, n_frames);
   if (grid) *grid = (int32_t)g;
   if (waves) *waves = (int32_t)(g * 4);
   return TFX_OK;

@@ -145,9 +145,10 @@ int grid_for(const tfx_handle_s *h, long items) {
 
 // Grid of the kernels that take a wavefront per (env, tile), four to a workgroup (k_clone, k_measure, k_cells): a few
 // workgroups per compute unit stride over more; TFX_MEASURE_GRID caps the measures' and the cells' launches instead
-// (tests of their stride loops; TFX_GRID_CAP caps the others, and these too where TFX_MEASURE_GRID is not set)
-long tile_grid(const tfx_handle_s *h, bool measure = false) {
-  long grid = ((long)h->d.E * h->d.G + 3) / 4;
+// (tests of their stride loops; TFX_GRID_CAP caps the others, and these too where TFX_MEASURE_GRID is not set).
+// n_frames > 0: k_frames' launch, capped like the cells' - its items are (frame, tile) pairs of the frames drawn
+long tile_grid(const tfx_handle_s *h, bool measure = false, long n_frames = 0) {
+  long grid = ((n_frames > 0 ? n_frames : (long)h->d.E) * h->d.G + 3) / 4;
   const bool own = measure && h->measure_grid > 0;
   const long cap = own ? (long)h->measure_grid : (long)h->n_cu * 16;
   if (grid > cap) grid = cap;

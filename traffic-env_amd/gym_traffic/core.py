@@ -192,6 +192,7 @@ class TfxEngine(object):
         self._cars = torch.zeros((E, R), dtype=torch.int32, device=dev)
         self._measures = None       # road_measures(): made on first use
         self._cells = {}            # road_cells(): made on first use, per number of cells
+        self._frames = {}           # frames(): made on first use, per (frames, px); holds the background after that
         b = nat.TfxBuffers()
         b.xv = _ptr(self._t if self._t is not None else self._ring)
         b.w = _ptr(self._tw if self._tw is not None else self._ringw)
@@ -470,6 +471,52 @@ class TfxEngine(object):
         """(workgroups, wavefronts) of the road_cells launch of this engine for n_cells cells (tfx_cells_launch; tests)."""
         g, w = C.c_int32(), C.c_int32()
         nat.check(self.lib.tfx_cells_launch(self.h, int(n_cells), C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def frame_size(self, px=32):
+        """(H, W) of a frame at px pixels per road length (tfx_frame_size): ((m + 1) * px + 1, (n + 1) * px + 1)."""
+        hh, ww = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_frame_size(self.h, int(px), C.byref(hh), C.byref(ww)))
+        return int(hh.value), int(ww.value)
+
+    def frames(self, env_ids=None, px=32, out=None, roads_only=False):
+        """Top-view pictures of chosen envs, from one read-only launch over their live cars (tfx_frames, include/tfx.h;
+        gym_traffic.devrng.frames states the definition in NumPy) -> uint8 [n, H, W, 4] device tensor, bytes R, G, B, A
+        ([..., :3] is RGB): white background, every road in its light's colour, every car a blue bar.  env_ids: a list,
+        an array or an int32 device tensor of env numbers (None: every env; an id outside [0, E) gives a white frame;
+        repeats are fine); px: pixels per road length, 8 .. 256.  out: the caller's tensor of that shape; roads_only:
+        `out` already holds the background of an earlier call with the same px, write the road pixels only.  Default:
+        a tensor the engine keeps per (n, px) and reuses - from its second use on only the road pixels are written.
+        No host synchronisation when env_ids is None or a device tensor; nothing of the env state is written."""
+        if env_ids is None:
+            ids, n = None, self.E
+        else:
+            if not torch.is_tensor(env_ids):
+                env_ids = torch.as_tensor(np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1)))
+            ids = env_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            n = int(ids.shape[0])
+        px = int(px)
+        if not nat.FRAME_PX_MIN <= px <= nat.FRAME_PX_MAX:
+            raise ValueError("frames: px must be in %d .. %d" % (nat.FRAME_PX_MIN, nat.FRAME_PX_MAX))
+        if n < 1:
+            raise ValueError("frames: no env to draw")
+        shape = (n,) + self.frame_size(px) + (4,)
+        if out is None:
+            roads_only = (n, px) in self._frames
+            if not roads_only:
+                self._frames[(n, px)] = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            out = self._frames[(n, px)]
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("frames(out=): a contiguous uint8 [%d, %d, %d, 4] device tensor is needed" % shape[:3])
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_frames(self.h, _ptr(ids), n, px, _ptr(out), nat.FRAMES_ROADS_ONLY if roads_only else 0,
+                                          self._stream()))
+        return out
+
+    def frames_launch(self, n_frames, px=32):
+        """(workgroups, wavefronts) of the frames launch of this engine for n_frames frames (tfx_frames_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_frames_launch(self.h, int(n_frames), int(px), C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
 
     def head_rows(self):

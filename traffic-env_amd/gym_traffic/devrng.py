@@ -15,7 +15,8 @@ and return the rows of each tick next to its counts.
 `episode_phases` mirrors the other draw the device makes: the light phases of an env that restarts on the device
 (tfx_set_episodes, rule 2 of include/tfx.h).  `clone_plan` and `road_measures` state two more device rules in NumPy: which
 envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per road.  `road_cells` does the same for
-tfx_road_cells (cars and speeds per cell of road); `cell_edges` makes the uniform edges that leave no car out.
+tfx_road_cells (cars and speeds per cell of road); `cell_edges` makes the uniform edges that leave no car out.  `frames`
+states what tfx_frames draws (top-view RGBA pictures of chosen envs), `frame_geometry` where every road lies in them.
 
 `demand_tables`, `demand_segment` and `demand_counts` belong to the demand profiles (tfx_set_demand, rule 4 of
 include/tfx.h): the threshold tables the device reads, the segment of a clock tick, and the rule itself in NumPy - a pure
@@ -215,6 +216,107 @@ def road_cells(x, v, leading, lastcar, C, edges):
         cars[at] += 1
         total[at] = added[inr]
     return cars.reshape(shape + (B,)), total.reshape(shape + (B,))
+
+
+FRAME_GREEN, FRAME_YELLOW, FRAME_RED, FRAME_CAR = (0, 255, 0, 255), (255, 255, 0, 255), (255, 0, 0, 255), (0, 0, 255, 255)
+
+
+def frame_geometry(m, n, px):
+    """The roads of tfx_frames (include/tfx.h) on an m x n grid at px = S pixels per road length -> (start int64 [R, 2],
+    step int64 [R, 2], (H, W)): road e has the pixel t along it at (column, row) = start[e] + t * step[e] and owns t =
+    2 .. S - 2.  Train road d * m * n + row * n + col runs into the intersection centred at (cx, cy) = ((col + 1) * S,
+    (row + 1) * S), one pixel beside the centre line on the side of GridRoad._unit_segments' eps; the four exit blocks,
+    in that function's order, continue d = 3, 0, 2, 1 from the centre of their road's intersection away from the grid."""
+    m, n, S = int(m), int(n), int(px)
+    v = m * n
+    R = 4 * v + 2 * n + 2 * m
+    cell = np.arange(v)
+    cy, cx = (cell // n + 1) * S, (cell % n + 1) * S
+    start, step = np.zeros((R, 2), np.int64), np.zeros((R, 2), np.int64)
+    # per direction: offset of the start from the centre in units of S, offset beside the centre line, step
+    along = {0: ((-1, 0), (0, -1), (1, 0)), 1: ((1, 0), (0, 1), (-1, 0)), 2: ((0, -1), (1, 0), (0, 1)), 3: ((0, 1), (-1, 0), (0, -1))}
+
+    def put(roads, d, cx, cy, back):
+        (bx, by), (ox, oy), st = along[d]
+        start[roads, 0], start[roads, 1] = cx + back * bx * S + ox, cy + back * by * S + oy
+        step[roads] = st
+    for d in range(4):
+        put(slice(d * v, (d + 1) * v), d, cx, cy, 1)
+    b = 4 * v
+    j, i = np.arange(n), np.arange(m)
+    put(slice(b, b + n), 3, (j + 1) * S, S, 0)                            # out of row 0
+    put(slice(b + n, b + n + m), 0, n * S, (i + 1) * S, 0)                # out of the last column
+    put(slice(b + n + m, b + 2 * n + m), 2, (j + 1) * S, m * S, 0)        # out of the last row
+    put(slice(b + 2 * n + m, R), 1, S, (i + 1) * S, 0)                    # out of column 0
+    return start, step, ((m + 1) * S + 1, (n + 1) * S + 1)
+
+
+def _frame_pixel(t, top):
+    """clamp(floor(t), 0, top) in float32 before the conversion (a NaN gives 0)"""
+    with np.errstate(invalid="ignore"):
+        fl = np.floor(np.asarray(t, np.float32))
+        return np.where(fl >= 0, np.where(fl > top, top, fl), np.float32(0)).astype(np.int64)
+
+
+def frames(x, leading, lastcar, current_phase, elapsed, m, n, px, length, yellow_ticks=6, car_l=4.0, rows=None,
+           lengths=None, env_ids=None):
+    """The definition of tfx_frames (include/tfx.h) in NumPy -> uint8 [n_frames, H, W, 4] (R, G, B, A).  x float32 [E, R,
+    C] by ring slot (what tfx_export_ring produces), leading / lastcar int [E, R], current_phase / elapsed int [E, I] (the
+    light words of obs), m, n the grid, px = S pixels per road length, length the road length, yellow_ticks the
+    yellow time.  A car's length: car_l, or - with rows uint8 [E, R, C] (the archetype row of every ring slot) and
+    lengths float32 [rows of the table] - lengths[rows].  env_ids: the env of every frame (None: every env in order; an
+    id outside [0, E) gives an all-0xFF frame).  A pure function of its arguments: phases and destinations of the roads
+    are arithmetic on their ids, as in GridRoad.  Car j of a road sits in ring slot wrap(leading + 1 + j); with k =
+    float32(S - 3) / float32(length) it turns pixels t = 2 + b .. 2 + a blue, a = clamp(floor(x * k), 0, S - 4), b =
+    clamp(floor((x - l) * k), 0, S - 4), one float32 rounding per operation; a car whose x is NaN is not drawn."""
+    m, n, S = int(m), int(n), int(px)
+    if not 8 <= S <= 256:
+        raise ValueError("frames: px must be in 8 .. 256")
+    x = np.asarray(x, np.float32)
+    E, R, C = x.shape
+    v = m * n
+    if R != 4 * v + 2 * n + 2 * m:
+        raise ValueError("frames: x holds %d roads, an %d x %d grid has %d" % (R, m, n, 4 * v + 2 * n + 2 * m))
+    ld_all = np.asarray(leading, np.int64).reshape(E, R)
+    lc_all = np.asarray(lastcar, np.int64).reshape(E, R)
+    phase_now = np.asarray(current_phase, np.int64).reshape(E, v)
+    age = np.asarray(elapsed, np.int64).reshape(E, v)
+    ids = np.arange(E) if env_ids is None else np.asarray(env_ids, np.int64).reshape(-1)
+    start, step, (H, W) = frame_geometry(m, n, S)
+    k = np.float32(S - 3) / np.float32(length)
+    top = np.float32(S - 4)
+    road = np.arange(4 * v)
+    road_phase, dst = (road < 2 * v).astype(np.int64), road % v
+    out = np.full((len(ids), H, W, 4), 255, np.uint8)
+    t_own = np.arange(2, S - 1)
+    for f, env in enumerate(ids):
+        if not 0 <= env < E:
+            continue
+        mine = road_phase == phase_now[env, dst]
+        fresh = age[env, dst] < int(yellow_ticks)
+        colour = np.empty((R, 4), np.uint8)
+        colour[:] = FRAME_GREEN
+        colour[:4 * v][mine & fresh] = FRAME_YELLOW
+        colour[:4 * v][mine != fresh] = FRAME_RED
+        for e in range(R):
+            cols = start[e, 0] + t_own * step[e, 0]
+            rws = start[e, 1] + t_own * step[e, 1]
+            line = np.empty((S - 3, 4), np.uint8)
+            line[:] = colour[e]
+            ld, lc = int(ld_all[env, e]), int(lc_all[env, e])
+            slot = ld
+            for _ in range(lc - ld + (C - 1 if ld > lc else 0)):
+                slot = slot + 1 if slot + 1 < C else 1
+                xj = x[env, e, slot]
+                if np.isnan(xj):
+                    continue
+                lj = np.float32(car_l if rows is None else np.asarray(lengths, np.float32)[int(rows[env, e, slot])])
+                with np.errstate(invalid="ignore", over="ignore"):
+                    a = int(_frame_pixel(np.float32(xj * k), top))
+                    b = int(_frame_pixel(np.float32(np.float32(xj - lj) * k), top))
+                line[b:a + 1] = FRAME_CAR
+            out[f, rws, cols] = line
+    return out
 
 
 def gap_table(cars_per_tick, tail=1e-12):

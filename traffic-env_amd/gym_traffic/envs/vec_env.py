@@ -384,5 +384,22 @@ class TrafficVecEnv(object):
         image[:, 1] = torch.where(cnt > 0, tot / cnt.clamp(min=1) / float(v_scale), torch.zeros_like(tot))
         return VecCells(rc.n_cars, rc.speed_sum, image)
 
+    def frames(self, envs=None, px=32):
+        """Top-view pictures of chosen envs, on the device, with no host synchronisation (TfxEngine.frames / tfx_frames,
+        include/tfx.h) -> uint8 [len(envs), H, W, 4] device tensor, H = (m + 1) * px + 1, W = (n + 1) * px + 1, bytes R, G,
+        B, A: [..., :3] is the RGB picture a video logger keeps, [..., :3].permute(0, 3, 1, 2) the channels-first image
+        an agent reads - white background, roads in their lights' colours, cars as blue bars.  envs: a list, an array or
+        an int32 device tensor of env numbers (None: every env).  The engine keeps one tensor per (len(envs), px): the
+        next call with the same two overwrites it - clone() what must last."""
+        return self.engine.frames(envs, px=px)
+
+    def render(self, env=0, mode='rgb_array', px=32):
+        """One env's picture on the host -> uint8 NumPy [H, W, 3] (synchronises; frames() is the batched, device-side
+        form)."""
+        if mode != 'rgb_array':
+            raise NotImplementedError("TrafficVecEnv.render draws mode='rgb_array' only - there is no window for mode=%r; "
+                                      "take frames(envs, px) and show or save the images yourself" % (mode,))
+        return self.frames([int(env)], px=px)[0, ..., :3].cpu().numpy()
+
     def cars_on_roads(self):
         return self.engine.cars_on_roads()
