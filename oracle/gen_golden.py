@@ -15,7 +15,7 @@ Instrumentation (wrappers around reference callables; no reference logic is chan
   * `advance_finished_cars` / `advance_hack` are wrapped to snapshot the state
     between `move_cars` and the advance (the "mid" state) for kernel-level parity.
 
-Usage:  python oracle/gen_golden.py [--only NAME]
+Usage:  python oracle/gen_golden.py [--only NAME] [--set main|params]
 """
 import argparse
 import json
@@ -34,12 +34,12 @@ OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
 SCENARIOS = {}
 
 
-def scen(name, **kw):
+def scen(name, _table=None, **kw):
     d = dict(m=2, n=2, L=250.0, C=20, seed=0, T=300, poisson=True, rate=0.5, lcps=0.12,
              entry='all', learn_switch=False, mode='train', actions='random10',
              remi_every=10, state_every=1, state_next=False, mid=False, archetypes=None)
     d.update(kw)
-    SCENARIOS[name] = d
+    (SCENARIOS if _table is None else _table)[name] = d
 
 
 for _s in (0, 1, 2, 3):
@@ -77,6 +77,44 @@ scen("g2x2_archetypes_fractional_delta", seed=9, T=300, lcps=0.25,
 scen("g64x64_c130_ints", m=64, n=64, L=800.0, C=130, seed=0, T=130, state_every=0)
 
 
+# ---- the second list: runs OFF the reference's defaults, written to tests/golden/params/ -----------------------------
+# `rate` other than a power of two (every product with it rounds), `rate` = 1 (coarse steps: cars overshoot v0), one
+# ordinary archetype row other than the reference's, several rows at such a rate, the reference's module constants
+# replaced, line grids (m = 1 or n = 1) and roads of a few cars.  The subfolder keeps them out of the parametrised
+# tests over tests/golden/*.npz; tests/test_oracle_params.py and tests/test_gpu_params.py read them.
+OUT_PARAMS = os.path.join(OUT, "params")
+PARAM_SCENARIOS = {}
+ONE_ROW = [[9.0, 5, 2, 4, 12.0, 5, 2, 1.5]]
+TRUCK = [[8.0, 8, 1.5, 4, 10.0, 4, 2.5, 2]]
+
+
+def pscen(name, **kw):
+    kw.setdefault("T", 240)
+    scen(name, _table=PARAM_SCENARIOS, **kw)
+
+
+pscen("rate03", L=120.0, C=16, seed=11, rate=0.3, lcps=0.2)
+pscen("rate07", L=120.0, C=16, seed=12, rate=0.7, lcps=0.2)
+pscen("rate025", L=120.0, C=16, seed=13, rate=0.25, lcps=0.2)
+pscen("rate1_light", L=250.0, C=20, seed=14, rate=1.0, lcps=0.12)
+pscen("rate1", L=75.0, C=10, seed=15, rate=1.0, lcps=0.2)
+pscen("one_row", L=120.0, C=16, seed=16, lcps=0.25, archetypes=ONE_ROW)
+pscen("truck_rate07", L=120.0, C=16, seed=17, rate=0.7, lcps=0.2, archetypes=TRUCK)
+pscen("line_1x3", m=1, n=3, L=120.0, C=12, seed=18, lcps=0.25)
+pscen("line_3x1", m=3, n=1, L=120.0, C=12, seed=19, lcps=0.25)
+pscen("line_1x1", m=1, n=1, L=120.0, C=12, seed=20, lcps=0.5)
+pscen("short_2x3_c6", m=2, n=3, L=30.0, C=6, seed=21, lcps=0.2)
+pscen("short_2x2_c5_rate1", L=20.0, C=5, seed=22, rate=1.0, lcps=0.15)
+pscen("short_2x2_c4_rate1_validate", L=12.0, C=4, seed=23, rate=1.0, lcps=0.15, mode='validate')
+pscen("three_rows_rate07", L=120.0, C=16, seed=24, rate=0.7, lcps=0.2,
+      archetypes=[[11.11, 4, 3, 4, 13.89, 6, 2, 1], [8.0, 8, 1.5, 4, 10.0, 4, 2.5, 2], [12.0, 3.5, 4, 2, 16.0, 7, 1.5, 1]])
+# the reference's module constants (traffic_env.py:17-25) replaced the way CAPACITY is; the detection distance is a
+# literal there (:201) and stays 10
+pscen("constants", L=120.0, C=16, seed=25, lcps=0.3,
+      constants=dict(yellow_ticks=4, thresh=0.35, overflow_penalty=7, eps=3e-7))
+REF_CONSTANT_NAMES = dict(yellow_ticks="YELLOW_TICKS", thresh="THRESH", overflow_penalty="OVERFLOW_PENALTY", eps="EPS")
+
+
 def run(name, sc, mods):
     te = mods["gym_traffic.envs.traffic_env"]
     rg = mods["gym_traffic.envs.roadgraph"]
@@ -91,6 +129,9 @@ def run(name, sc, mods):
     C = te.CAPACITY
     xi, vi, wi = te.xi, te.vi, te.wi
     keep_archetypes = te.archetypes
+    keep_constants = {ref: getattr(te, ref) for ref in REF_CONSTANT_NAMES.values()}
+    for k, val in (sc.get("constants") or {}).items():
+        setattr(te, REF_CONSTANT_NAMES[k], val)
     arch_cols = [te.vi, te.li, te.ai, te.deltai, te.v0i, te.bi, te.ti, te.s0i]
     if sc.get("archetypes"):
         tab = np.zeros((len(sc["archetypes"]), te.params), np.float32)
@@ -258,6 +299,8 @@ def run(name, sc, mods):
         te.advance_finished_cars = orig_adv
         te.advance_hack = orig_hack
         te.archetypes = keep_archetypes
+        for ref, val in keep_constants.items():
+            setattr(te, ref, val)
 
 
 def live_planes(state, leading, lastcar, C, planes):
@@ -282,14 +325,18 @@ def live_planes(state, leading, lastcar, C, planes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
+    ap.add_argument("--set", default="all", choices=["all", "main", "params"],
+                    help="main: tests/golden/, params: tests/golden/params/ (the runs off the defaults)")
     a = ap.parse_args()
     mods = load_reference()
-    os.makedirs(OUT, exist_ok=True)
-    for name, sc in SCENARIOS.items():
+    todo = [(OUT, n, sc) for n, sc in SCENARIOS.items() if a.set != "params"]
+    todo += [(OUT_PARAMS, n, sc) for n, sc in PARAM_SCENARIOS.items() if a.set != "main"]
+    for folder, name, sc in todo:
         if a.only and a.only != name:
             continue
+        os.makedirs(folder, exist_ok=True)
         out = run(name, sc, mods)
-        path = os.path.join(OUT, name + ".npz")
+        path = os.path.join(folder, name + ".npz")
         np.savez_compressed(path, **out)
         print("%-24s T=%d spawned=%d overflow_ticks=%d trips=%d  %.1f KB" % (
             name, sc["T"], int(out["generated_cars"]), int(out["done"].sum()),

@@ -20,7 +20,7 @@ F = np.float32
 
 class NumpyBatchedEnv(object):
     def __init__(self, m, n, length, capacity, dest, phases, nexts, n_envs=1, rate=0.5,
-                 v=11.11, l=4.0, a=3.0, v0=13.89, b=6.0, T=2.0, s0=1.0):
+                 v=11.11, l=4.0, a=3.0, v0=13.89, b=6.0, T=2.0, s0=1.0, constants=None):
         self.m, self.n, self.E, self.C = int(m), int(n), int(n_envs), int(capacity)
         self.I = self.m * self.n
         self.r = 4 * self.I
@@ -29,8 +29,10 @@ class NumpyBatchedEnv(object):
         self.length, self.rate = F(length), F(rate)
         self.cv, self.cl, self.ca, self.cv0, self.cb, self.cT, self.cs0 = (F(t) for t in (v, l, a, v0, b, T, s0))
         self.two_sab = F(2.0) * np.sqrt(self.ca * self.cb, dtype=F)
-        self.eps, self.thresh, self.near_end = F(1e-8), F(0.2), F(self.length - F(10.0))
-        self.yellow, self.ovf_pen = 6, F(10.0)
+        k = dict(yellow_ticks=6, thresh=0.2, detect_dist=10.0, overflow_penalty=10.0, eps=1e-8)   # traffic_env.py:17-25
+        k.update(constants or {})
+        self.eps, self.thresh, self.near_end = F(k["eps"]), F(k["thresh"]), F(self.length - F(k["detect_dist"]))
+        self.yellow, self.ovf_pen = int(k["yellow_ticks"]), F(k["overflow_penalty"])
         E, R, C, I, r = self.E, self.R, self.C, self.I, self.r
         self.x = np.zeros((E, R, C), F)
         self.v = np.zeros((E, R, C), F)

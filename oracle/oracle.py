@@ -27,6 +27,9 @@ ARCHETYPE[BI] = 6
 ARCHETYPE[TI] = 2
 ARCHETYPE[S0I] = 1
 
+# module constants of the reference (traffic_env.py:17-25; detect_dist is the literal of :201)
+CONSTANTS = dict(yellow_ticks=6, thresh=0.2, detect_dist=10.0, overflow_penalty=10.0, eps=1e-8)
+
 
 class OrcCfg(C.Structure):
     _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("I", C.c_int32), ("r", C.c_int32),
@@ -75,7 +78,9 @@ class OracleEnv(object):
     """
 
     def __init__(self, m, n, length, capacity, dest, phases, nexts, n_envs=1, rate=0.5,
-                 learn_switch=False, validate=False, archetype=None, trip_cap=4096):
+                 learn_switch=False, validate=False, archetype=None, trip_cap=4096, constants=None):
+        """archetype: float32 [10], the one row cars are made of (default: the reference's); constants: entries of
+        CONSTANTS to override."""
         self.m, self.n, self.E, self.C = int(m), int(n), int(n_envs), int(capacity)
         self.I = self.m * self.n
         self.r = 4 * self.I
@@ -91,11 +96,13 @@ class OracleEnv(object):
         arch = ARCHETYPE if archetype is None else np.asarray(archetype, np.float32)
         for k in range(NPARAMS):
             c.archetype[k] = float(arch[k])
-        c.yellow_ticks = 6
-        c.thresh = 0.2
-        c.detect_dist = 10.0
-        c.overflow_penalty = 10.0
-        c.eps = 1e-8
+        unknown = set(constants or {}) - set(CONSTANTS)
+        if unknown:
+            raise ValueError("unknown constants: %s" % sorted(unknown))
+        self.constants = dict(CONSTANTS, **(constants or {}))
+        c.yellow_ticks = int(self.constants["yellow_ticks"])
+        for k in ("thresh", "detect_dist", "overflow_penalty", "eps"):
+            setattr(c, k, float(self.constants[k]))
         c.learn_switch = int(bool(learn_switch))
         c.validate = int(bool(validate))
         self.cfg = c

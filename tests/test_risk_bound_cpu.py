@@ -18,14 +18,32 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from gym_traffic.envs.roadgraph import GridRoad  # noqa: E402
 
 
-@pytest.mark.parametrize("rate", [0.25, 0.5, 1.0])
+@pytest.mark.parametrize("rate", [0.25, 0.3, 0.5, 0.7, 1.0])
 @pytest.mark.parametrize("sorted_x", [True, False])
 def test_no_car_moves_beyond_the_reach_k_risk_computes(rate, sorted_x):
-    rng = np.random.RandomState(int(rate * 100) + int(sorted_x))
+    reach_holds(rate, sorted_x, None)
+
+
+# v, l, a, delta, v0, b, T, s0: a single ordinary row other than the reference's (a = 2) and the truck (a = 1.5) - the
+# bound takes the row's own a, at rates whose products round
+@pytest.mark.parametrize("rate,row", [(0.3, [9.0, 5, 2, 4, 12.0, 5, 2, 1.5]), (0.7, [8.0, 8, 1.5, 4, 10.0, 4, 2.5, 2]),
+                                      (0.5, [9.0, 5, 2, 4, 12.0, 5, 2, 1.5]), (1.0, [8.0, 8, 1.5, 4, 10.0, 4, 2.5, 2])])
+@pytest.mark.parametrize("sorted_x", [True, False])
+def test_the_bound_with_a_single_row_other_than_the_default(rate, row, sorted_x):
+    reach_holds(rate, sorted_x, row)
+
+
+def reach_holds(rate, sorted_x, row):
+    rng = np.random.RandomState(int(rate * 100) + int(sorted_x) + (0 if row is None else int(10 * row[2])))
     m, n, C, length, E = 3, 2, 20, 150.0, 6
     g = GridRoad(m, n, length)
-    orc = OracleEnv(m, n, length, C, g.dest, g.phases, g.nexts, n_envs=E, rate=rate)
-    a_max = np.float32(3.0)                       # the archetype's a (traffic_env.py:36)
+    archetype = None
+    if row is not None:
+        archetype = np.zeros(10, np.float32)
+        archetype[1:9] = row
+    orc = OracleEnv(m, n, length, C, g.dest, g.phases, g.nexts, n_envs=E, rate=rate, archetype=archetype)
+    a_max = np.float32(3.0 if row is None else row[2])   # the archetype's a (traffic_env.py:36)
+    car_l = np.float32(4.0 if row is None else row[1])
     r32 = np.float32(rate)
     half_ar2 = (np.float32(0.5) * (a_max * r32)) * r32
     checked = left = 0
@@ -36,7 +54,7 @@ def test_no_car_moves_beyond_the_reach_k_risk_computes(rate, sorted_x):
             v[rng.rand(*v.shape) < 0.05] = 3e7
             v[rng.rand(*v.shape) < 0.05] = 1e-30
             pick = rng.rand(*x[:, :, 2:].shape) < 0.1
-            x[:, :, 2:][pick] = (x[:, :, 1:-1] - np.float32(4.0))[pick]
+            x[:, :, 2:][pick] = (x[:, :, 1:-1] - car_l)[pick]
             np.put_along_axis(x, leading[:, :, None].astype(np.int64), np.inf, axis=2)
         orc.reset(rng.randint(2, size=orc.I).astype(np.int32))
         for k in range(E):

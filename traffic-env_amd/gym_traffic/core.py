@@ -82,11 +82,14 @@ class PackedMirror(object):
 class TfxEngine(object):
     def __init__(self, m, n, length, capacity, n_envs=1, rate=0.5, learn_switch=False,
                  validate=False, entry_spec=0, planes=None, trip_cap=4096, device=None, env_id_offset=0,
-                 layout=None, archetypes=None):
-        """archetypes: rows (v, l, a, delta, v0, b, T, s0) of the reference's `archetypes` table
+                 layout=None, archetypes=None, constants=None):
+        """constants: entries of CONSTANTS to override (yellow_ticks, thresh, detect_dist, overflow_penalty, eps); the
+        engine keeps the full set as `constants`.
+        archetypes: rows (v, l, a, delta, v0, b, T, s0) of the reference's `archetypes` table
         (traffic_env.py:35-43) when there is more than its single default row, or a delta other than 4
         ("heterogeneous cars": needs planes = 3 and the transposed layout; every car keeps its row, see
-        set_spawns(..., rows=) and the `arch` property)."""
+        set_spawns(..., rows=) and the `arch` property).  One ordinary row (delta = 4) IS the engine's single archetype:
+        `car` (the car_* values in use) and cfg.car_* then hold that row, not ARCHETYPE."""
         if not torch.cuda.is_available():
             raise nat.TfxError("no GPU visible: the traffic env step runs on MI355X only (no CPU fallback)")
         self.lib = nat.lib()
@@ -99,7 +102,11 @@ class TfxEngine(object):
         cfg = nat.TfxConfig()
         cfg.m, cfg.n, cfg.capacity, cfg.n_envs, cfg.planes = self.m, self.n, self.C, self.E, self.P
         cfg.length, cfg.rate = float(length), float(rate)
-        for k, v in ARCHETYPE.items():
+        self.car = dict(ARCHETYPE)
+        if arch is not None and not self.het:
+            self.car = dict(zip(("car_v", "car_l", "car_a", "car_delta", "car_v0", "car_b", "car_T", "car_s0"),
+                                [float(t) for t in arch[0]]))
+        for k, v in self.car.items():
             setattr(cfg, k, v)
         if arch is not None:
             if len(arch) > nat.MAX_ARCH:
@@ -108,7 +115,12 @@ class TfxEngine(object):
             for a, row in enumerate(arch):
                 for j in range(8):
                     cfg.arch[a][j] = float(row[j])
-        for k, v in CONSTANTS.items():
+        unknown = set(constants or {}) - set(CONSTANTS)
+        if unknown:
+            raise ValueError("unknown constants: %s (known: %s)" % (sorted(unknown), sorted(CONSTANTS)))
+        self.constants = dict(CONSTANTS, **(constants or {}))
+        self.constants["yellow_ticks"] = int(self.constants["yellow_ticks"])
+        for k, v in self.constants.items():
             setattr(cfg, k, v)
         cfg.learn_switch, cfg.validate = int(bool(learn_switch)), int(bool(validate))
         cfg.entry_spec = int(entry_spec)

@@ -56,8 +56,11 @@ VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
 class TrafficVecEnv(object):
     def __init__(self, num_envs, m, n, length, capacity=20, rate=0.5, local_cars_per_sec=0.12,
                  spawn='poisson', spawn_period=8, entry_spec=0, learn_switch=False, validate=False,
-                 seed=0, env_id_offset=0, device=None, archetypes=None, autoreset=False, episode_len=None, demand=None):
-        """archetypes: None (the reference's single archetype) or float [n, 8] rows (v, l, a, delta, v0, b, T, s0) of
+                 seed=0, env_id_offset=0, device=None, archetypes=None, autoreset=False, episode_len=None, demand=None,
+                 constants=None):
+        """constants: entries of gym_traffic.core.CONSTANTS to override (the reference's module constants: yellow_ticks,
+        thresh, detect_dist, overflow_penalty, eps), handed to the engine.
+        archetypes: None (the reference's single archetype) or float [n, 8] rows (v, l, a, delta, v0, b, T, s0) of
         the archetype table, n <= 64 - every spawn mode then makes mixed cars as the module docstring says.
         autoreset / episode_len: episodes on the device, see the module docstring (episode_len needs autoreset; in
         validate mode the trip log of an ended episode stays readable until the next decision begins).
@@ -70,15 +73,18 @@ class TrafficVecEnv(object):
         self._ctor = dict(m=m, n=n, length=length, capacity=capacity, rate=rate, local_cars_per_sec=local_cars_per_sec,
                           spawn=spawn, spawn_period=spawn_period, entry_spec=entry_spec, learn_switch=learn_switch,
                           validate=validate, seed=seed, env_id_offset=env_id_offset, device=device,
-                          archetypes=archetypes, autoreset=autoreset, episode_len=episode_len, demand=demand)
+                          archetypes=archetypes, autoreset=autoreset, episode_len=episode_len, demand=demand,
+                          constants=constants)
         self.graph = GridRoad(m, n, length)
         self.graph.generate_entrypoints(entry_spec)
         tab = None if archetypes is None else np.asarray(archetypes, np.float32).reshape(-1, 8)
         self.engine = TfxEngine(m, n, length, capacity, n_envs=num_envs, rate=rate,
                                 learn_switch=learn_switch, validate=validate,
                                 entry_spec=entry_spec, device=device, env_id_offset=env_id_offset,
-                                archetypes=tab, **({} if tab is None else dict(planes=3, layout="transposed")))
+                                archetypes=tab, constants=constants,
+                                **({} if tab is None else dict(planes=3, layout="transposed")))
         self.archetypes = tab
+        self.constants = self.engine.constants
         self.rate = float(rate)
         open_sides = 4 - bin(int(entry_spec) & 15).count('1')
         self.cars_per_sec = local_cars_per_sec * m * open_sides
