@@ -617,6 +617,79 @@ int tfx_frames(tfx_handle h, const int32_t *env_ids, int32_t n_frames, int32_t p
 /* Test support: the launch geometry tfx_frames uses for this handle, n_frames and px - workgroups, and wavefronts (one
  * per (frame, tile) item at a time). */
 int tfx_frames_launch(tfx_handle h, int32_t n_frames, int32_t px, int32_t *grid, int32_t *waves);
+/* Travel times on the device.  Mean travel time is the headline figure of signal control and the one thing the
+ * reference's validate mode prints (advance_hack, traffic_env.py:139-157).  Two read-only launches (k_ages, k_trips,
+ * csrc/tfx_travel.hpp) give it with no host round trip: the ages of the cars still on the map, and the finished trips
+ * reduced where they are logged.  Without them the route is a copy of the whole [E][trip_cap] log, and tfx_export_ring of
+ * every ring slot for the spawn ticks - and a mean over finished trips alone flatters the policy that leaves its cars in
+ * a jam.
+ *
+ * tfx_car_ages: how long every live car has been on the map.  Definition, as a function of the image tfx_export_ring
+ * would produce at that moment, with the cars and the car order of tfx_road_measures.  `now` is the handle's device
+ * clock, read on the device when the launch runs (the way tfx_clone_envs reads it): the value tfx_get_tick returns once
+ * the stream has drained.  The age of a car is int32(side_age(now, side word)) (csrc/tfx_common.hpp) - TWICE the trip time
+ * in seconds advance_hack would log if the car left the map in this tick:
+ *   single-archetype handles   (int32)((float)now - w)               w: the spawn tick, a float
+ *   heterogeneous handles      (now - spawn tick) & 0xFFFFFF          spawn ticks are kept modulo 2^24
+ * Per road:
+ *   n_cars    the cars on the road, what tfx_cars_on_roads returns
+ *   age_sum   the int64 sum of their ages
+ *   age_max   the largest of their ages, 0 on an empty road
+ * Integer arithmetic: order-free, the same bits on both layouts and from a host loop (gym_traffic/devrng.py car_ages).
+ * Outputs are device pointers, [E][R] by the reference's road id; any may be NULL, at least one must not be.  Without
+ * TFX_TRAVEL_ACCUMULATE every bound output is overwritten; with it n_cars and age_sum are added to and age_max is maxed.
+ *
+ * One launch on `stream`, no host synchronisation; nothing in the handle or in the caller's bound state is written:
+ * captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the launch.  TFX_MEASURE_GRID and
+ * TFX_GRID_CAP cap the launch as they cap the measures'.  TFX_EINVAL: a NULL `out`, a NULL handle, all three pointers
+ * NULL, unknown flag bits; TFX_ESTATE before tfx_bind_buffers, or on a handle that carries no side plane (planes == 2).
+ * A refused call launches nothing. */
+typedef struct tfx_age_buffers {
+  int32_t *n_cars;     /* [E][R] by road id; may be NULL */
+  int64_t *age_sum;
+  int32_t *age_max;
+} tfx_age_buffers;
+enum { TFX_TRAVEL_ACCUMULATE = 1 };
+int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *stream);
+/* Test support: the launch geometry tfx_car_ages uses for this handle - workgroups, and wavefronts (one per (env, tile)
+ * item at a time), like tfx_measure_launch. */
+int tfx_ages_launch(tfx_handle h, int32_t *grid, int32_t *waves);
+/* tfx_trip_stats: the finished trips of every env, reduced on the device.  Needs a validate handle with trip_times and
+ * n_trips bound.  edges: a HOST array of n_bins + 1 non-decreasing int32 values in ticks, copied into the kernel's
+ * arguments; n_bins is 1..32.  cursor: a DEVICE int32 [E] the caller owns, or NULL.  Outputs: device pointers, [E], hist
+ * [E][n_bins]; any may be NULL, at least one must not be; with hist NULL, edges may be NULL and n_bins 0.
+ *
+ * Rule, for env e, with cap = trip_cap:
+ *   n = n_trips[e];  c = cursor[e] if cursor is given and 0 <= cursor[e] <= n, else 0 (a log shorter than its cursor was
+ *   cleared by a reset or a restart: it is read from the start)
+ *   the entries taken are i in [min(c, cap), min(n, cap)); entry i counts t_i = (int32)(trip_times[e][i] * 2.0f) ticks -
+ *   exact, the log holds age / 2.0f of an integer age
+ *   count     the number of entries taken
+ *   tick_sum  the int64 sum of t_i (seconds: / 2, as the reference has them)
+ *   tick_max  their maximum, 0 if none were taken
+ *   lost      max(n, cap) - max(c, cap): the trips that happened but fell off the end of the log
+ *   hist[b]   the number of i with edges[b] <= t_i < edges[b + 1] (equal neighbours: an empty bin)
+ *   afterwards, if cursor is given, cursor[e] = n
+ * Without TFX_TRAVEL_ACCUMULATE the outputs are overwritten; with it sums and counts are added to and tick_max is maxed.
+ * Everything is integer, so nothing depends on the order.  gym_traffic/devrng.py trip_stats states the rule in NumPy.
+ *
+ * The rule cannot see one case: a log that was cleared and then grew back past the old cursor before the next call looks
+ * like a log that only grew.  The caller zeroes the cursor of the envs it resets (TrafficVecEnv.travel_times does).
+ *
+ * One launch on `stream`, no host synchronisation; nothing in the handle or in its bound state is written (the cursor and
+ * the outputs are the caller's): captured graphs stay valid, tfx_debug_fail_after does not count the launch.  TFX_EINVAL:
+ * a NULL `out`, a NULL handle, all outputs NULL, unknown flag bits, n_bins out of range, hist given without edges, edges
+ * that decrease; TFX_ESTATE before tfx_bind_buffers, or on a handle that is not in validate mode.  A refused call
+ * launches nothing. */
+typedef struct tfx_trip_stat_buffers {
+  int32_t *count;      /* [E]; may be NULL */
+  int64_t *tick_sum;
+  int32_t *tick_max;
+  int32_t *lost;
+  int32_t *hist;       /* [E][n_bins]; may be NULL */
+} tfx_trip_stat_buffers;
+int tfx_trip_stats(tfx_handle h, const int32_t *edges, int32_t n_bins, int32_t *cursor, const tfx_trip_stat_buffers *out,
+                   int32_t flags, void *stream);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

@@ -23,6 +23,7 @@
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
 #include "tfx_sequence.hpp"
+#include "tfx_travel.hpp"
 
 namespace {
 
@@ -1170,6 +1171,67 @@ int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   const long g = tile_grid(h, true);
   if (grid) *grid = (int32_t)g;
   if (waves) *waves = (int32_t)(g * 4);
+  return TFX_OK;
+}
+
+int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *stream) {
+  if (!out) return fail(TFX_EINVAL, "ages: out is null");
+  if (int rc = check_handle(h, false)) return rc;
+  if (!out->n_cars && !out->age_sum && !out->age_max) return fail(TFX_EINVAL, "ages: every output pointer is null");
+  if (flags & ~TFX_TRAVEL_ACCUMULATE) return fail(TFX_EINVAL, "unknown travel flags 0x%x", flags);
+  if (int rc = check_handle(h, true)) return rc;
+  if (!h->d.w) return fail(TFX_ESTATE, "ages: the handle carries no side plane (planes == 2): spawn ticks are not kept");
+  AgeOut o{};
+  o.n_cars = out->n_cars;
+  o.age_sum = reinterpret_cast<long long *>(out->age_sum);
+  o.age_max = out->age_max;
+  o.accumulate = (flags & TFX_TRAVEL_ACCUMULATE) ? 1 : 0;
+  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
+  hipLaunchKernelGGL(k_ages, dim3((unsigned)tile_grid(h, true)), dim3(256), 0, (hipStream_t)stream, h->d, o);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+int tfx_ages_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  const long g = tile_grid(h, true);
+  if (grid) *grid = (int32_t)g;
+  if (waves) *waves = (int32_t)(g * 4);
+  return TFX_OK;
+}
+
+int tfx_trip_stats(tfx_handle h, const int32_t *edges, int32_t n_bins, int32_t *cursor, const tfx_trip_stat_buffers *out,
+                   int32_t flags, void *stream) {
+  // (the arguments first, as tfx_road_cells checks them: each cause is named whatever state the handle is in)
+  if (!out) return fail(TFX_EINVAL, "trips: out is null");
+  if (int rc = check_handle(h, false)) return rc;
+  if (!out->count && !out->tick_sum && !out->tick_max && !out->lost && !out->hist)
+    return fail(TFX_EINVAL, "trips: every output pointer is null");
+  if (flags & ~TFX_TRAVEL_ACCUMULATE) return fail(TFX_EINVAL, "unknown travel flags 0x%x", flags);
+  if (n_bins < 0 || n_bins > TRIP_BINS || (out->hist && n_bins < 1))
+    return fail(TFX_EINVAL, "trips: n_bins %d is outside 1..%d", n_bins, TRIP_BINS);
+  TripEdges ed{};
+  if (out->hist) {
+    if (!edges) return fail(TFX_EINVAL, "trips: hist is given but edges is null");
+    for (int k = 0; k < n_bins; ++k)
+      if (edges[k] > edges[k + 1])
+        return fail(TFX_EINVAL, "trips: edges decrease at %d (%d, %d)", k, edges[k], edges[k + 1]);
+    for (int k = 0; k <= TRIP_BINS; ++k) ed.e[k] = edges[k <= n_bins ? k : n_bins];
+  }
+  if (int rc = check_handle(h, true)) return rc;
+  if (!h->d.validate || !h->d.trip_times || !h->d.n_trips)
+    return fail(TFX_ESTATE, "trips: the handle is not in validate mode with trip_times and n_trips bound: no trip log is kept");
+  TripOut o{};
+  o.count = out->count;
+  o.tick_sum = reinterpret_cast<long long *>(out->tick_sum);
+  o.tick_max = out->tick_max;
+  o.lost = out->lost;
+  o.hist = out->hist;
+  o.accumulate = (flags & TFX_TRAVEL_ACCUMULATE) ? 1 : 0;
+  // Not counted by tfx_debug_fail_after; only the caller's cursor and outputs are written: captured graphs stay valid.
+  hipLaunchKernelGGL(k_trips, dim3((unsigned)trips_grid(h)), dim3(256), 0, (hipStream_t)stream, h->d, ed,
+                     out->hist ? n_bins : 0, cursor, o);
+  HIPCHK(hipGetLastError());
   return TFX_OK;
 }
 

@@ -183,6 +183,16 @@ long demand_grid(const tfx_handle_s *h, int n_ticks) {
   return grid_capped(h, grid);
 }
 
+// Grid of k_trips (tfx_travel.hpp): a wavefront per env, four to a workgroup; a few workgroups per compute unit stride
+// over more.  (k_ages takes tile_grid's measure form, like k_measure.)
+long trips_grid(const tfx_handle_s *h) {
+  long grid = ((long)h->d.E + 3) / 4;
+  const long cap = (long)h->n_cu * 16;
+  if (grid > cap) grid = cap;
+  if (grid < 1) grid = 1;
+  return grid_capped(h, grid);
+}
+
 // Rule 4's rows for n_ticks clock ticks into `out` - from the device clock on (use_clock: the rows of a call about to
 // be enqueued on st) or from tick0 on (the preview).  One launch; it writes nothing but `out`.
 int launch_demand(tfx_handle h, int use_clock, int tick0, int n_ticks, int *out, hipStream_t st) {

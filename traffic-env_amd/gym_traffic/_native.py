@@ -14,6 +14,8 @@ CLONE_STREAM, CLONE_EPISODE = 1, 2      # flags of tfx_clone_envs
 MEASURE_ACCUMULATE = 1                  # flag of tfx_road_measures
 CELLS_ACCUMULATE = 1                    # flag of tfx_road_cells
 MAX_CELLS = 32                          # TFX_MAX_CELLS
+TRAVEL_ACCUMULATE = 1                   # flag of tfx_car_ages and tfx_trip_stats
+MAX_TRIP_BINS = 32                      # the most bins tfx_trip_stats takes
 FRAMES_ROADS_ONLY = 1                   # flag of tfx_frames
 FRAME_PX_MIN, FRAME_PX_MAX = 8, 256     # TFX_FRAME_PX_MIN, TFX_FRAME_PX_MAX
 DEMAND_MAX_PROFILES, DEMAND_MAX_SEGMENTS, DEMAND_MAX_CDF = 16, 64, 256   # limits of tfx_set_demand
@@ -50,6 +52,15 @@ class TfxMeasureBuffers(C.Structure):
 
 class TfxCellBuffers(C.Structure):
     _fields_ = [("n_cars", C.c_void_p), ("speed_sum", C.c_void_p)]
+
+
+class TfxAgeBuffers(C.Structure):
+    _fields_ = [("n_cars", C.c_void_p), ("age_sum", C.c_void_p), ("age_max", C.c_void_p)]
+
+
+class TfxTripStatBuffers(C.Structure):
+    _fields_ = [("count", C.c_void_p), ("tick_sum", C.c_void_p), ("tick_max", C.c_void_p), ("lost", C.c_void_p),
+                ("hist", C.c_void_p)]
 
 
 class TfxDemand(C.Structure):
@@ -122,6 +133,10 @@ _PROTOS = {
     "tfx_measure_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tfx_road_cells": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(TfxCellBuffers), C.c_int32, C.c_void_p]),
     "tfx_cells_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_car_ages": (C.c_int, [C.c_void_p, C.POINTER(TfxAgeBuffers), C.c_int32, C.c_void_p]),
+    "tfx_ages_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_trip_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(TfxTripStatBuffers),
+                                 C.c_int32, C.c_void_p]),
     "tfx_frame_size": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tfx_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "tfx_frames_launch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

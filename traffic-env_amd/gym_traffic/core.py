@@ -33,6 +33,10 @@ CONSTANTS = dict(yellow_ticks=6, thresh=0.2, detect_dist=10.0, overflow_penalty=
 RoadMeasures = collections.namedtuple("RoadMeasures", "n_cars n_halted queue speed_sum")
 # what road_cells() returns: two [E, R, B] device tensors by road id and cell (tfx_road_cells, include/tfx.h)
 RoadCells = collections.namedtuple("RoadCells", "n_cars speed_sum")
+# what car_ages() returns: three [E, R] device tensors by road id (tfx_car_ages, include/tfx.h)
+CarAges = collections.namedtuple("CarAges", "n_cars age_sum age_max")
+# what trip_stats() returns: [E] device tensors, hist [E, n_bins] or None (tfx_trip_stats, include/tfx.h)
+TripStats = collections.namedtuple("TripStats", "count tick_sum tick_max lost hist")
 
 
 def _ptr(t):
@@ -203,6 +207,8 @@ class TfxEngine(object):
         self.trip_times = torch.zeros((E, self.trip_cap), dtype=torch.float32, device=dev) if validate else None
         self._cars = torch.zeros((E, R), dtype=torch.int32, device=dev)
         self._measures = None       # road_measures(): made on first use
+        self._ages = None           # car_ages(): made on first use
+        self._trips = {}            # trip_stats(): made on first use, per number of bins
         self._cells = {}            # road_cells(): made on first use, per number of cells
         self._frames = {}           # frames(): made on first use, per (frames, px); holds the background after that
         b = nat.TfxBuffers()
@@ -446,6 +452,80 @@ class TfxEngine(object):
         g, w = C.c_int32(), C.c_int32()
         nat.check(self.lib.tfx_measure_launch(self.h, C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
+
+    def car_ages(self, accumulate=False, out=None):
+        """How long every live car has been on the map, per road, from one read-only launch over the side plane
+        (tfx_car_ages, include/tfx.h; gym_traffic.devrng.car_ages states the definition in NumPy): -> CarAges(n_cars
+        int32, age_sum int64, age_max int32), [E, R] device tensors by road id.  Ages are in ticks at the engine's device
+        clock - twice the seconds advance_hack would log if the car left the map now.  accumulate: n_cars and age_sum
+        are added to and age_max is maxed instead of overwritten.  out: the caller's CarAges (any member None: not
+        computed); default: tensors the engine allocates once, zeroed, and reuses.  Needs the side plane (planes == 3:
+        validate mode or heterogeneous cars).  No host synchronisation; nothing of the env state is written."""
+        want = dict(n_cars=torch.int32, age_sum=torch.int64, age_max=torch.int32)
+        if out is None:
+            if self._ages is None:
+                self._ages = CarAges(*[torch.zeros((self.E, self.R), dtype=want[f], device=self.device)
+                                       for f in CarAges._fields])
+            out = self._ages
+        else:
+            out = CarAges(*out)
+            for name, t in zip(CarAges._fields, out):
+                if t is not None and (t.dtype != want[name] or tuple(t.shape) != (self.E, self.R) or not t.is_contiguous()
+                                      or not t.is_cuda):
+                    raise ValueError("car_ages(out=): %s must be a contiguous %s [%d, %d] device tensor"
+                                     % (name, want[name], self.E, self.R))
+        b = nat.TfxAgeBuffers()
+        b.n_cars, b.age_sum, b.age_max = [_ptr(t) for t in out]
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_car_ages(self.h, C.byref(b), nat.TRAVEL_ACCUMULATE if accumulate else 0, self._stream()))
+        return out
+
+    def ages_launch(self):
+        """(workgroups, wavefronts) of the car_ages launch of this engine (tfx_ages_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_ages_launch(self.h, C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def trip_stats(self, edges=None, cursor=None, accumulate=False, out=None):
+        """The finished trips of every env, reduced on the device where they are logged (tfx_trip_stats, include/tfx.h;
+        gym_traffic.devrng.trip_stats states the rule in NumPy): -> TripStats(count int32, tick_sum int64, tick_max
+        int32, lost int32 [E], hist int32 [E, n_bins] or None).  Trips count in ticks (seconds * 2).  edges: n_bins + 1
+        non-decreasing ints in ticks (host), 1 .. 32 bins; None: no histogram.  cursor: the caller's int32 [E] device
+        tensor - only the log entries from cursor[e] on are taken and cursor[e] becomes n_trips[e]; an env whose log is
+        shorter than its cursor is read from the start; zero the cursor of the envs you reset.  None: the whole log.
+        lost: trips that happened but fell off the end of the log (trip_cap).  accumulate: sums and counts are added to
+        and tick_max is maxed.  out: the caller's TripStats (any member None: not computed); default: tensors the engine
+        allocates once per n_bins, zeroed, and reuses.  Needs validate mode.  No host synchronisation."""
+        e = None if edges is None else np.ascontiguousarray(np.asarray(edges, np.int32).reshape(-1))
+        B = 0 if e is None else len(e) - 1
+        if e is not None and not 1 <= B <= nat.MAX_TRIP_BINS:
+            raise ValueError("trip_stats: %d edges - 2 .. %d make 1 .. %d bins" % (len(e), nat.MAX_TRIP_BINS + 1,
+                                                                                  nat.MAX_TRIP_BINS))
+        want = dict(count=torch.int32, tick_sum=torch.int64, tick_max=torch.int32, lost=torch.int32, hist=torch.int32)
+        shape = lambda f: (self.E, B) if f == "hist" else (self.E,)   # noqa: E731
+        if out is None:
+            if B not in self._trips:
+                self._trips[B] = TripStats(*[None if (f == "hist" and B == 0) else
+                                             torch.zeros(shape(f), dtype=want[f], device=self.device)
+                                             for f in TripStats._fields])
+            out = self._trips[B]
+        else:
+            out = TripStats(*out)
+            for name, t in zip(TripStats._fields, out):
+                if t is not None and (t.dtype != want[name] or tuple(t.shape) != shape(name) or not t.is_contiguous()
+                                      or not t.is_cuda):
+                    raise ValueError("trip_stats(out=): %s must be a contiguous %s %s device tensor"
+                                     % (name, want[name], list(shape(name))))
+        if cursor is not None and (not isinstance(cursor, torch.Tensor) or cursor.dtype != torch.int32
+                                   or tuple(cursor.shape) != (self.E,) or not cursor.is_contiguous() or not cursor.is_cuda):
+            raise ValueError("trip_stats(cursor=): a contiguous int32 [%d] device tensor is needed" % self.E)
+        b = nat.TfxTripStatBuffers()
+        b.count, b.tick_sum, b.tick_max, b.lost, b.hist = [_ptr(t) for t in out]
+        ep = None if e is None else e.ctypes.data_as(C.POINTER(C.c_int32))
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_trip_stats(self.h, ep, B, _ptr(cursor), C.byref(b),
+                                              nat.TRAVEL_ACCUMULATE if accumulate else 0, self._stream()))
+        return out
 
     def road_cells(self, edges, accumulate=False, out=None):
         """Cars and speeds per cell of road, from one read-only launch over the live cars (tfx_road_cells, include/tfx.h;

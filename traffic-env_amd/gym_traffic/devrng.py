@@ -17,6 +17,8 @@ and return the rows of each tick next to its counts.
 envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per road.  `road_cells` does the same for
 tfx_road_cells (cars and speeds per cell of road); `cell_edges` makes the uniform edges that leave no car out.  `frames`
 states what tfx_frames draws (top-view RGBA pictures of chosen envs), `frame_geometry` where every road lies in them.
+`car_ages` and `trip_stats` state the travel-time rules (tfx_car_ages, tfx_trip_stats): the ages of the live cars per
+road, and the finished trips of every env's log reduced from a cursor on.
 
 `demand_tables`, `demand_segment` and `demand_counts` belong to the demand profiles (tfx_set_demand, rule 4 of
 include/tfx.h): the threshold tables the device reads, the segment of a clock tick, and the rule itself in NumPy - a pure
@@ -163,6 +165,74 @@ def road_measures(x, v, leading, lastcar, C, halt_speed=0.1, x_from=None):
         queue += unbroken & live
         total = np.where(inr, added, total)
     return cars.reshape(shape), halted.reshape(shape), queue.reshape(shape), total.reshape(shape)
+
+
+def car_ages(w, leading, lastcar, C, now, het=False):
+    """The definition of tfx_car_ages (include/tfx.h) in NumPy, over the ring plane w float32 [..., R, C] of spawn ticks
+    by ring slot (what tfx_export_ring produces; heterogeneous handles: the spawn tick modulo 2^24), leading / lastcar
+    int [..., R], `now` the handle's clock.  -> (n_cars int32, age_sum int64, age_max int32), [..., R].  Car j of a road
+    sits in slot wrap(leading + 1 + j); its age is int32(float32(now) - w), or with het (now - spawn tick) & 0xFFFFFF -
+    twice the trip time in seconds advance_hack would log for it in this tick.  age_max is 0 on an empty road."""
+    C = int(C)
+    w = np.asarray(w, np.float32)
+    shape = w.shape[:-1]
+    w = w.reshape(-1, C)
+    ld = np.asarray(leading, np.int64).reshape(-1)
+    lc = np.asarray(lastcar, np.int64).reshape(-1)
+    n = lc - ld + np.where(ld > lc, C - 1, 0)
+    rows = np.arange(len(ld))
+    total = np.zeros(len(ld), np.int64)
+    oldest = np.zeros(len(ld), np.int32)
+    for j in range(C - 1):
+        live = j < n
+        slot = ld + 1 + j
+        slot = np.where(slot > C - 1, slot - (C - 1), slot)
+        slot = np.where(live, slot, 0)
+        wj = w[rows, slot]
+        if het:
+            age = ((int(now) - wj.astype(np.int64)) & 0xFFFFFF).astype(np.int32)
+        else:
+            with np.errstate(invalid="ignore"):
+                age = (np.float32(int(now)) - wj).astype(np.float32).astype(np.int32)
+        age = np.where(live, age, 0).astype(np.int32)
+        total += age
+        oldest = np.maximum(oldest, age)
+    return n.astype(np.int32).reshape(shape), total.reshape(shape), oldest.reshape(shape)
+
+
+def trip_stats(trip_times, n_trips, trip_cap, cursor=None, edges=None):
+    """The rule of tfx_trip_stats (include/tfx.h) in NumPy: trip_times float32 [E, trip_cap] (seconds, as advance_hack
+    logs them), n_trips int [E], cursor int [E] or None, edges n_bins + 1 non-decreasing ints in ticks or None.
+    -> (count int32 [E], tick_sum int64 [E], tick_max int32 [E], lost int32 [E], hist int32 [E, n_bins] or None,
+    new_cursor int32 [E]).  Env e: n = n_trips[e]; c = cursor[e] if 0 <= cursor[e] <= n else 0; the entries i in
+    [min(c, cap), min(n, cap)) count t_i = int32(trip_times[e, i] * 2) ticks; lost = max(n, cap) - max(c, cap);
+    hist[b] = #{i: edges[b] <= t_i < edges[b + 1]}; new_cursor = n."""
+    cap = int(trip_cap)
+    tt = np.asarray(trip_times, np.float32).reshape(-1, cap)
+    n_trips = np.asarray(n_trips, np.int64).reshape(-1)
+    E = len(n_trips)
+    cur = np.zeros(E, np.int64) if cursor is None else np.asarray(cursor, np.int64).reshape(-1)
+    ed = None if edges is None else np.asarray(edges, np.int64).reshape(-1)
+    count = np.zeros(E, np.int32)
+    tick_sum = np.zeros(E, np.int64)
+    tick_max = np.zeros(E, np.int32)
+    lost = np.zeros(E, np.int32)
+    hist = None if ed is None else np.zeros((E, len(ed) - 1), np.int32)
+    for e in range(E):
+        n = int(n_trips[e])
+        c = int(cur[e])
+        if c < 0 or c > n:
+            c = 0
+        lo, hi = min(c, cap), min(n, cap)
+        t = (tt[e, lo:max(lo, hi)] * np.float32(2.0)).astype(np.int32)
+        count[e] = len(t)
+        tick_sum[e] = t.astype(np.int64).sum()
+        tick_max[e] = t.max() if len(t) else 0
+        lost[e] = max(n, cap) - max(c, cap)
+        if ed is not None:
+            for b in range(len(ed) - 1):
+                hist[e, b] = np.count_nonzero((t >= ed[b]) & (t < ed[b + 1]))
+    return count, tick_sum, tick_max, lost, hist, n_trips.astype(np.int32)
 
 
 def cell_edges(length, n_cells):

@@ -35,6 +35,10 @@ no episode starts on an empty map.  `make_warm_pool` pays that warm-up once, for
 `set_warm_pool` attaches it: from then on a restart on the device is a clone of one of the pool's envs (which one: rule 3
 of include/tfx.h, devrng.episode_pool_slots) instead of an empty map, still inside the decision's one submission;
 `reset(warm=True)` starts episode 0 the same way.
+
+Travel times: in validate mode `travel_times()` keeps mean travel time on the device - the finished trips of every env's
+log reduced from a cursor on (tfx_trip_stats) and the ages of the cars still on the map (tfx_car_ages), running across
+resets and restarts, with no host round trip; `trip_times()` remains the host copy of the log.
 """
 import collections
 
@@ -42,7 +46,7 @@ import numpy as np
 import torch
 
 from gym_traffic import devrng
-from gym_traffic.core import ARCHETYPE, TfxEngine
+from gym_traffic.core import ARCHETYPE, TfxEngine, TripStats
 from gym_traffic.envs.roadgraph import GridRoad
 from gym_traffic.spawner import ArrivalStreams
 
@@ -51,13 +55,16 @@ from gym_traffic.spawner import ArrivalStreams
 VecMeasures = collections.namedtuple("VecMeasures", "n_cars n_halted queue speed_sum halted cars mean_speed pressure")
 # what TrafficVecEnv.cell_obs() returns: the engine's two per-cell tensors and the image a convolutional policy reads
 VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
+# what TrafficVecEnv.travel_times() returns: per-env travel-time figures, finished trips and cars still on the map
+VecTravel = collections.namedtuple("VecTravel", "finished finished_s mean_trip_s max_trip_s hist lost unfinished "
+                                                "unfinished_s oldest_s mean_incl_unfinished_s")
 
 
 class TrafficVecEnv(object):
     def __init__(self, num_envs, m, n, length, capacity=20, rate=0.5, local_cars_per_sec=0.12,
                  spawn='poisson', spawn_period=8, entry_spec=0, learn_switch=False, validate=False,
                  seed=0, env_id_offset=0, device=None, archetypes=None, autoreset=False, episode_len=None, demand=None,
-                 constants=None):
+                 constants=None, trip_cap=4096):
         """constants: entries of gym_traffic.core.CONSTANTS to override (the reference's module constants: yellow_ticks,
         thresh, detect_dist, overflow_penalty, eps), handed to the engine.
         archetypes: None (the reference's single archetype) or float [n, 8] rows (v, l, a, delta, v0, b, T, s0) of
@@ -65,7 +72,9 @@ class TrafficVecEnv(object):
         autoreset / episode_len: episodes on the device, see the module docstring (episode_len needs autoreset; in
         validate mode the trip log of an ended episode stays readable until the next decision begins).
         demand: with spawn='demand', the keyword arguments of TfxEngine.set_demand other than the seed - means, weights,
-        seg_ticks, tick_offset, n_cdf (single-archetype envs only)."""
+        seg_ticks, tick_offset, n_cdf (single-archetype envs only).
+        trip_cap: validate mode, the trips every env's log holds between two restarts (later ones are counted, not
+        kept: travel_times().lost)."""
         if episode_len is not None and not autoreset:
             raise ValueError("episode_len needs autoreset=True (the time limit is kept on the device)")
         self.num_envs = int(num_envs)
@@ -74,14 +83,14 @@ class TrafficVecEnv(object):
                           spawn=spawn, spawn_period=spawn_period, entry_spec=entry_spec, learn_switch=learn_switch,
                           validate=validate, seed=seed, env_id_offset=env_id_offset, device=device,
                           archetypes=archetypes, autoreset=autoreset, episode_len=episode_len, demand=demand,
-                          constants=constants)
+                          constants=constants, trip_cap=trip_cap)
         self.graph = GridRoad(m, n, length)
         self.graph.generate_entrypoints(entry_spec)
         tab = None if archetypes is None else np.asarray(archetypes, np.float32).reshape(-1, 8)
         self.engine = TfxEngine(m, n, length, capacity, n_envs=num_envs, rate=rate,
                                 learn_switch=learn_switch, validate=validate,
                                 entry_spec=entry_spec, device=device, env_id_offset=env_id_offset,
-                                archetypes=tab, constants=constants,
+                                archetypes=tab, constants=constants, trip_cap=trip_cap,
                                 **({} if tab is None else dict(planes=3, layout="transposed")))
         self.archetypes = tab
         self.constants = self.engine.constants
@@ -132,6 +141,11 @@ class TrafficVecEnv(object):
             self.episode_return, self.episode_length = eng.ep_return, eng.ep_len
             self.final_return, self.final_length = eng.final_return, eng.final_len
             self.episode_index = eng.ep_index
+        self._travel = None     # travel_times(): the cursor and the running tensors, made on first use
+        # validate mode with autoreset: ep_index as it stood when the last decision began (a reset, a clone: as it stands
+        # with nothing pending).  Where ep_index has moved since, the episode ended in that decision and the NEXT decision
+        # begins by restarting the env - which clears its trip log (_begin_decision)
+        self._ep_before = eng.ep_index.clone() if (self.autoreset and eng.n_trips is not None) else None
 
     @property
     def observation_shape(self):
@@ -146,6 +160,9 @@ class TrafficVecEnv(object):
         if phase_init is None:
             phase_init = self._phase_rng.randint(2, size=(eng.E, eng.I)).astype(np.int32)
         eng.reset(phase_init)
+        self._travel_forget()
+        if self._ep_before is not None:
+            self._ep_before.copy_(eng.ep_index)     # (the reset clears the restart marks; ep_index does not move)
         if warm:
             pool = self.warm_pool
             if pool is None:
@@ -210,6 +227,7 @@ class TrafficVecEnv(object):
         if phase_init is None:
             phase_init = self._phase_rng.randint(2, size=(eng.E, eng.I)).astype(np.int32)
         eng.reset_envs(mask, phase_init)
+        self._travel_forget(mask)
         return mask
 
     def step(self, actions=None, n_ticks=1, cycle_period=None):
@@ -239,7 +257,23 @@ class TrafficVecEnv(object):
             eng.set_actions(actions)
         if self.spawn in ('poisson', 'regular'):
             self._bind_arrivals(n)
+        if self._ep_before is not None:
+            self._begin_decision()
         return eng.agent_step(n, remi=remi)
+
+    def _begin_decision(self):
+        """Validate mode with autoreset, on the device: the envs whose episode ended in the previous decision restart as
+        this one begins, which clears their trip logs - travel_times() reads those from the start again."""
+        ep = self.engine.ep_index
+        if self._travel is not None:
+            self._travel["cursor"].masked_fill_(ep != self._ep_before, 0)
+        self._ep_before.copy_(ep)
+
+    def _restart_pending(self):
+        """int32 [E] on the device: 1 where the env's last decision ended its episode and no decision has begun since"""
+        if self._ep_before is None:
+            return torch.zeros((self.num_envs,), dtype=torch.int32, device=self.engine.device)
+        return (self.engine.ep_index != self._ep_before).to(torch.int32)
 
     def _bind_arrivals(self, n):
         """The host streams' next n ticks as the engine's per-tick spawn counts (and, heterogeneous cars, rows)."""
@@ -274,17 +308,27 @@ class TrafficVecEnv(object):
         if streams and self.spawn != other.spawn:
             raise ValueError("clone_envs(streams=True) needs the same spawn mode in both envs (%r / %r)"
                              % (self.spawn, other.spawn))
-        idx = eng.clone_envs(src_of_env, source=other.engine, streams=bool(streams and on_device),
-                             episodes=bool(episodes and self.autoreset and other.autoreset))
-        if streams and self.spawn == 'demand':
-            # the envs the clone applied to (devrng.clone_plan's rule, on the device) take their sources' profiles
+        with_episodes = bool(episodes and self.autoreset and other.autoreset)
+        idx = eng.clone_envs(src_of_env, source=other.engine, streams=bool(streams and on_device), episodes=with_episodes)
+        demand = streams and self.spawn == 'demand'
+        if demand or self._travel is not None or (with_episodes and self._ep_before is not None):
+            # the envs the clone applied to (devrng.clone_plan's rule, on the device)
             s = idx.long()
             ok = (s >= 0) & (s < other.num_envs)
             sc = s.clamp(0, other.num_envs - 1)
             if other is self:
                 t = s[sc]
                 ok &= (t == -1) | (t == s)
-            self.demand_profile.copy_(torch.where(ok, other.demand_profile[sc], self.demand_profile))
+            if demand:      # ... take their sources' profiles
+                self.demand_profile.copy_(torch.where(ok, other.demand_profile[sc], self.demand_profile))
+            if self._travel is not None:
+                # ... and their sources' trip logs: travel_times() goes on from the end of what was cloned, so the
+                # source's finished trips do not enter the clone's running figures
+                cur = self._travel["cursor"]
+                cur.copy_(torch.where(ok, eng.n_trips, cur))
+            if with_episodes and self._ep_before is not None:
+                # ... and, with the episode accounting, their sources' restart marks
+                self._ep_before.copy_(torch.where(ok, eng.ep_index - other._restart_pending()[sc], self._ep_before))
         if streams and self.spawn in ('poisson', 'regular'):
             from gym_traffic.devrng import clone_plan
             host = idx.cpu().numpy()
@@ -300,8 +344,12 @@ class TrafficVecEnv(object):
         return snap
 
     def restore(self, snap):
-        """Every env back to the state `snap` (from snapshot()) holds."""
-        return self.clone_envs(torch.arange(self.num_envs, dtype=torch.int32), source=snap)
+        """Every env back to the state `snap` (from snapshot()) holds.  travel_times() reads the restored logs from the
+        start: its running figures go on, and the trips the snapshot's logs hold are added to them (clear the running
+        figures before restoring if they counted those trips once already)."""
+        idx = self.clone_envs(torch.arange(self.num_envs, dtype=torch.int32), source=snap)
+        self._travel_forget()
+        return idx
 
     # ---- validate-mode metrics, batched (reference: traffic_test.py:41-46, traffic_env.py:139-157, util.py:91-92) ----
     def light_times(self, actions):
@@ -332,6 +380,78 @@ class TrafficVecEnv(object):
         if env is not None:
             return tt[env, :min(int(n[env]), eng.trip_cap)].copy()
         return [tt[k, :min(int(n[k]), eng.trip_cap)].copy() for k in range(eng.E)]
+
+    def _travel_forget(self, mask=None):
+        """The trip logs of the envs in `mask` (None: all) start again: travel_times() reads them from the start."""
+        if self._travel is None:
+            return
+        cur = self._travel["cursor"]
+        if mask is None:
+            cur.zero_()
+        else:
+            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
+            cur.masked_fill_(m.to(cur.device).bool(), 0)
+
+    def travel_times(self, edges_s=None, clear=False):
+        """Travel times of every env, on the device, with no host synchronisation: one launch over the trip logs
+        (TfxEngine.trip_stats / tfx_trip_stats) and one over the live cars' spawn ticks (TfxEngine.car_ages /
+        tfx_car_ages, include/tfx.h) plus a few torch expressions.  Needs validate=True.  The env keeps a cursor into every
+        env's log and RUNNING tensors: each call adds the trips logged since the previous one, across resets and
+        restarts, so a rollout reads "mean travel time so far" at any decision.  -> VecTravel, all [E]:
+            finished      int64    trips read from the logs so far
+            finished_s    float64  the sum of their trip seconds (ticks / 2, as the reference logs them)
+            mean_trip_s   float64  finished_s / finished, 0 where no trip finished
+            max_trip_s    float64  the longest of them
+            hist          int64 [E, n_bins]: trips per bin of edges_s (seconds, n_bins + 1 non-decreasing values, rounded
+                          to ticks; at most 32 bins), None without edges_s; changing the edges restarts the histogram
+            lost          int64    trips that happened but fell off the end of a log (trip_cap): counted in no other figure
+            unfinished    int64    cars on the map NOW, on all R roads - exit roads too: a car logs its trip only when it
+                          leaves the map
+            unfinished_s  float64  the seconds those cars have spent on the map so far
+            oldest_s      float64  the longest of those
+            mean_incl_unfinished_s  float64  (finished_s + unfinished_s) / (finished + unfinished), 0 where that is 0 / 0 -
+                          the figure that does not flatter a policy whose cars never arrive
+        clear=True zeroes the running tensors after the read (per-episode or per-window figures).
+        reset(), reset_done(mask) and restore() zero the cursor of the envs they reset; clone_envs() sets the cursor of a
+        cloned env to the end of the log it received.  With autoreset=True call travel_times() ONCE PER DECISION, after
+        it: an ended episode's log stays readable only until the next decision begins; agent_step() zeroes the cursor
+        of every env whose episode ended in the previous decision as it begins the next one, because the restart clears
+        that log (a snapshot carries which envs are about to restart, so this holds across snapshot() / restore() too).
+        Calls between two decisions add nothing twice.  A warm pool's n_trips must be zero for the log of a restart to
+        start empty: make_warm_pool leaves it so, a pool that is stepped afterwards must be re-zeroed by the caller."""
+        eng = self.engine
+        if eng.n_trips is None:
+            raise RuntimeError("travel times are recorded in validate mode only (TrafficVecEnv(..., validate=True))")
+        E, dev = eng.E, eng.device
+        ed = None if edges_s is None else tuple(int(round(2.0 * float(t))) for t in np.asarray(edges_s).reshape(-1))
+        tv = self._travel
+        if tv is None:
+            tv = self._travel = dict(cursor=torch.zeros((E,), dtype=torch.int32, device=dev),
+                                     count=torch.zeros((E,), dtype=torch.int32, device=dev),
+                                     tick_sum=torch.zeros((E,), dtype=torch.int64, device=dev),
+                                     tick_max=torch.zeros((E,), dtype=torch.int32, device=dev),
+                                     lost=torch.zeros((E,), dtype=torch.int32, device=dev), hist=None, edges=None)
+        if ed != tv["edges"]:
+            tv["edges"] = ed
+            tv["hist"] = None if ed is None else torch.zeros((E, len(ed) - 1), dtype=torch.int32, device=dev)
+        eng.trip_stats(edges=ed, cursor=tv["cursor"], accumulate=True,
+                       out=TripStats(tv["count"], tv["tick_sum"], tv["tick_max"], tv["lost"], tv["hist"]))
+        ages = eng.car_ages()
+        finished = tv["count"].long()
+        finished_s = tv["tick_sum"].double() / 2
+        zero = torch.zeros_like(finished_s)
+        unfinished = ages.n_cars.sum(dim=1, dtype=torch.int64)
+        unfinished_s = ages.age_sum.sum(dim=1).double() / 2
+        both = finished + unfinished
+        out = VecTravel(finished, finished_s, torch.where(finished > 0, finished_s / finished.clamp(min=1), zero),
+                        tv["tick_max"].double() / 2, None if tv["hist"] is None else tv["hist"].long(), tv["lost"].long(),
+                        unfinished, unfinished_s, ages.age_max.max(dim=1).values.double() / 2,
+                        torch.where(both > 0, (finished_s + unfinished_s) / both.clamp(min=1), zero))
+        if clear:
+            for k in ("count", "tick_sum", "tick_max", "lost", "hist"):
+                if tv[k] is not None:
+                    tv[k].zero_()
+        return out
 
     def measures(self, halt_speed=0.1, x_from=None, accumulate=False):
         """The standard traffic measures of signal control for every env, on the device, with no host synchronisation:
