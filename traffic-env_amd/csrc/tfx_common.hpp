@@ -1,4 +1,4 @@
-// tfx_common.hpp - device parameter block and the arithmetic every kernel shares.
+// tfx_common.hpp - the arithmetic every kernel shares (the device parameter block itself: tfx_dev_layout.hpp).
 //
 // Float contract (bit-for-bit shared with oracle/idm_oracle.c): binary32, the reference's
 // expression order (gym_traffic/envs/traffic_env.py:50-62), one rounding per operation
@@ -11,127 +11,14 @@
 #include <cstdint>
 
 #include "tfx.h"
+#include "tfx_dev_layout.hpp"
 #include "tfx_pow.h"
 
 namespace tfx {
 
-constexpr int KP = TFX_KP;
-
-// Everything a kernel needs, passed by value.
-struct Dev {
-  int I, r, R, C, E, n_entry, obs_len;
-  int yellow, learn_switch, validate, env_off;
-  // fused agent step (Repeater + Remi, traffic_test.py:27-64): `passed` (and, without Remi, the
-  // rewards) accumulate over the ticks of the step; an env that overflowed in an earlier tick of
-  // the step stands still for the rest of it (`if done: break`, traffic_test.py:55)
-  int agent_mode, accum_rewards;
-  const int *agent_first;  // tick at which the current agent step began
-  float length, rate, car_v, car_l, car_a, car_v0, car_b, car_T, car_s0;
-  float risk_a;                  // the largest acceleration any car can have (k_risk's movement bound): car_a, or the table's maximum
-  float two_sab, eps, thresh, near_end, ovf_pen;
-  float r_two_sab, r_v0;  // correctly rounded reciprocals of the two constant divisors
-  int fastdiv;            // the reciprocal form of those divisions was verified exact (div_selftest)
-  int fastmax;            // v_max_f32 orders +0 above -0 in either operand order (k_max_selftest)
-  // caller-owned state
-  float2 *xv;  // [E][R][C] (x, v) per ring slot
-  float *w;    // [E][R][C] spawn tick per ring slot, or nullptr
-  int *leading, *lastcar, *obs;
-  // phase | elapsed of env k's intersections: lights + k * lights_stride (= obs + 2r, obs_len: the words inside obs
-  // - or a workgroup's LDS copy with stride 0, k_tail)
-  int *lights;
-  int lights_stride;
-  float *rewards;
-  int *waiting;
-  uint8_t *passed_dst;
-  int *done_tick;
-  float *trip_times;
-  int *n_trips;
-  int trip_cap;
-  // handle-owned tables + scratch
-  const int *nexts, *pred, *entry_idx;
-  // transposed layout: road e of an env lives in storage slot road_slot[e] (tile = slot / 64, lane =
-  // slot % 64, G tiles per env); slot_road is the inverse (-1 = padding lane)
-  const int *road_slot, *slot_road;
-  int G;
-  int trows;  // rows (of 64 (x, v) pairs) a tile occupies in T: >= C - 2
-  int4 *rec;      // per road: {pops k | head slot << 16, spawn overflows | uncompacted << 30, bits of post-move tail x, live cars}
-  // transposed layout: rows at the top of a road's column that hold no car (0..TFX_KP; see rec_hb) - a byte per road
-  // of its own since round 4: the pass reads one byte instead of a 16-byte record, k_tail writes one back
-  uint8_t *hb;
-  // k_tail<AGENT> only (LDS): 0 = the road's head cannot reach the road's end in the next tick - what edge_tile saw while
-  // it held the head's new state - so that the bound for the next pair (risk_lane) need not load the road's first rows
-  uint8_t *riskhint;
-  // "road state word": leading | lastcar << 9 | hb << 18 of a road, 4 bytes.  Between the pairs of ONE tfx_step call
-  // (plain cars, outside agent steps) k_tail writes this word instead of leading, lastcar and hb (9 bytes) and the next
-  // pass reads it instead of them (its RSW form); the call's last k_tail brings the reference's arrays up to date, its
-  // first pass reads those - nobody else looks at them in between.
-  int *rsw;
-  // per road, two-tick pass only (tfx_move_tt.hpp): what the pass hands to the edge work of the second tick, 12 bytes
-  // (round 3: one 16-byte record): {v of the tail after the first tick, x of the tail after the second} and the
-  // waiting (both ticks so far) | detected (second tick so far) | detected (first tick) counts (rec2c_pack)
-  float2 *rec2f;
-  int *rec2c;
-  // A two-tick pass that k_tail follows (its CREC form) writes its road record in 8 bytes instead of rec's 16 - {packed
-  // integers (crec_pack), bits of the tail's x} - and the count of spawn overflows, when there are any, to ovf_cnt; k_tail expands it into its LDS copy
-  // of rec, so the phase code reads what it always read
-  int2 *crec;
-  int *ovf_cnt;
-  // transposed layout only (tfx_config.layout = 1): xv is T[tile][k][64]; the first TFX_KP = 2 cars that
-  // left a road this tick wait in its outbox column outb[tile][j][64], j < KP - a road that pops more
-  // stays uncompacted for the tick and its env takes the serial advance; the fake leader's x has no
-  // slot of its own and lives in leadx
-  float2 *outb;
-  float *outw;  // outbox of the spawn-tick plane (planes = 3)
-  float *leadx;
-  int layout;
-  float *tailx;   // per road: x of the last car after the advance (what update_lights reads)
-  int *env_flag;  // == tick+1 when the env must take the serial advance this tick
-  // == tick+1 when the env takes the pair of ticks starting at `tick` one tick at a time (k_risk).  Two planes, used in
-  // turn by the pairs of a call (risk_word): k_tail stamps the NEXT pair's plane while the launches behind it still read
-  // the current pair's
-  int *env_risk;
-  int risk_stride;  // words from one plane to the other (the whole handle's E, also inside the half of a split call)
-  int *risk_any;  // [2], one per plane of env_risk: == tick+1 when any env is marked for the pair starting at `tick`
-  unsigned long long *veh;
-  unsigned long long *slow_pairs;  // env-pairs of agent steps that k_tail took one tick at a time (tfx_slow_pairs)
-  int *tickA, *tickB;
-  // per-tick inputs
-  const int *action;
-  int action_mode, action_period;
-  long action_stride;
-  const int *spawn;
-  int spawn_mode, spawn_period;
-  long spawn_stride;
-  // greedy controller (algorithms/greedy.py:14-16): > 0 = the advance of tick t writes the action of tick t + 1
-  // whenever (t + 1) % greedy_spacing == 0
-  int greedy_spacing;
-  int *greedy_act;               // [E][I]
-  // heterogeneous cars (tfx_config.n_archetypes): every car's side word w holds (spawn tick mod 2^24) << 6 | table row as integer bits
-  int het;
-  const float *arch_tab;         // [TFX_MAX_ARCH][ARCH_W]: l, a, v0, T, s0, 2 sqrt(a b), delta, spawn speed
-  int *taila;                    // per road: table row of its last car (next to tailx)
-  const uint8_t *spawn_arch;     // rows of the cars the count buffer adds: [tick][E][n_entry][spawn_arch_S]
-  int spawn_arch_S;
-  long spawn_arch_stride;
-};
-
-// Episodes on the device (tfx_set_episodes, include/tfx.h), a parameter block of its own: only the kernels that begin
-// and end a decision (and k_reset) see it, every other kernel's arguments are what they were.  The caller's
-// accumulators, and two bytes per env of the handle's own - mark: the env's last decision ended its episode (the next
-// decision restarts it), last: the decision under way is the last one the time limit allows (k_episode_begin writes
-// it, the decision's tail reads it: nothing in a tail reads a word another lane of the same launch writes).
-struct EpDev {
-  int on, max;
-  unsigned seed_lo, seed_hi;
-  float *ep_return, *final_return;
-  int *ep_len, *final_len, *ep_index;
-  uint8_t *trunc, *mark, *last;
-};
-
 // The vehicle-update counter is spread over VEH_SLOTS words, one cache line apart: every wavefront
 // adds its share once, and with one word a small launch (one tile per wave, all waves finishing
 // together) spent ~25 us serialising 1280 atomics on it (cfg1 x 1024: k_move_t 30 us -> 5 us + walk).
-constexpr int VEH_SLOTS = 256, VEH_STRIDE = 8;
 __device__ __forceinline__ void veh_add(unsigned long long *veh, unsigned long long v) {
   const unsigned slot = (blockIdx.x * 4u + (threadIdx.x >> 6)) & (unsigned)(VEH_SLOTS - 1);
   atomicAdd(veh + (size_t)slot * VEH_STRIDE, v);

@@ -16,6 +16,7 @@
 #include "tfx_common.hpp"
 #include "tfx_misc.hpp"
 #include "tfx_demand.hpp"
+#include "tfx_dev_layout.hpp"
 #include "tfx_stream_layout.hpp"
 
 using namespace tfx;
@@ -109,7 +110,7 @@ struct tfx_handle_s {
   // themselves both halves start their passes together and only fall into step a pair or two later)
   int split_half = -1;
   bool split_first = false;
-  int *tick2 = nullptr;       // clock words of the second half (tickA, tickB), risk word
+  MiscWords *misc = nullptr;  // the small words of the scratch arena: the clock of the second half, clone_skipped
   bool het = false;           // heterogeneous cars (tfx_config.n_archetypes)
   float *dev_arch = nullptr;  // the archetype table on the device
   long long split_ticks = 0;  // ticks that ran split since tfx_create
@@ -139,7 +140,6 @@ struct tfx_handle_s {
   int move_blocks_per_cu = 0;  // TFX_MOVE_BLOCKS_PER_CU: workgroups per CU of the move kernels' grids (0: as measured)
   bool stagger = true;         // TFX_STAGGER=0: the second half's first pass does not wait for the first half's
   unsigned long long div_mismatches = 0;  // result of the reciprocal-division self-test
-  size_t n_tpairs = 0;                    // (x, v) pairs the xv buffer must hold in the transposed layout
   // fused agent step: the launch sequence of one step, captured once per (ticks, remi, inputs); tfx_step calls of
   // launch-bound handles replay a captured graph as well (tfx_hip.hip).  Both are captured on ag_stream.
   CapturedSeq captured[2];  // SEQ_AGENT, SEQ_STEP
@@ -162,9 +162,8 @@ struct tfx_handle_s {
   EpDev *dev_ep = nullptr;
   // warm restarts (tfx_set_episode_pool): the handle whose envs a restart clones, or null; the caller keeps it alive
   tfx_handle_s *pool = nullptr;
-  // tfx_clone_envs (tfx_clone.hpp): the device the handle lives on, the counter of envs left untouched
+  // tfx_clone_envs (tfx_clone.hpp): the device the handle lives on (the counter of envs left untouched: misc)
   int device = 0;
-  unsigned long long *clone_skipped = nullptr;
   // tfx_road_measures (tfx_measure.hpp): TFX_MEASURE_GRID=n caps its launch at n workgroups (tests of its stride loop)
   int measure_grid = 0;
   // TFX_GRID_CAP=n (test hook): every launch of a kernel that strides over its work takes at most n workgroups (0: off)
@@ -242,8 +241,6 @@ bool inject_failure(tfx_handle h) {
   do {                                                                                             \
     if (inject_failure(h)) return fail(TFX_EDEVICE, "injected launch failure (tfx_debug_fail_after)"); \
   } while (0)
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 int check_handle(tfx_handle h, bool need_bound) {
   if (!h) return fail(TFX_EINVAL, "null handle");

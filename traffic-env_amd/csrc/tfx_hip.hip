@@ -12,10 +12,12 @@
 //     Plain calls and agent steps enqueue them through ONE sequence (tfx_sequence.hpp: pair, single, run_ticks), which
 //     lists where the two differ.
 // This file is the C ABI itself; the handle is in tfx_handle.hpp, kernel choice, grid sizing and launches in tfx_launch.hpp,
-// the cold kernels in tfx_misc.hpp.  tfx_step and tfx_agent_step read alike: size the grids, decide, run the body
+// the cold kernels in tfx_misc.hpp, the table of an env's device arrays - the scratch arena tfx_create carves, the halves
+// of a split call (sub_dev), the pointer lists of graph_key - in tfx_dev_layout.hpp.  tfx_step and tfx_agent_step read alike: size the grids, decide, run the body
 // (step_body / agent_sequence) on the caller's stream or replay its capture (run_captured).
 #include <cmath>
 #include <initializer_list>
+#include <memory>
 #include <new>
 
 #include "tfx_cells.hpp"
@@ -27,40 +29,45 @@
 
 namespace {
 
+// A graph key is the values themselves, one after the other: every field has a fixed width, and the fields that come
+// and go (an array per mode, the pool's block) follow the modes and the pool pointer that announce them
+template <class... T>
+void key_put(std::string &key, const T &...v) {
+  (key.append(reinterpret_cast<const char *>(&v), sizeof v), ...);
+}
+void key_put_arrays(std::string &key, const Dev &d) {
+  for_each_env_array(d, [&key](const void *p, size_t, ArrayKind) { key_put(key, p); });
+}
+
 // The arrival stream's part of that key: k_poisson's / k_res's and k_demand's arguments - the kind, the seeds, the tables'
 // sizes, the caller's profile_of_env and the stream's buffer
-void stream_key(const ArrivalStream &a, char *key, size_t n) {
+void stream_key(const ArrivalStream &a, std::string &key) {
   const PoissonDev &p = a.ps;
   const DemandDev &m = a.dm;
-  snprintf(key, n, "|S%d.%u.%u.%d.%d.%d.%d|D%d.%d.%d.%d.%d.%u.%u|%p|%p", (int)a.kind, p.seed_lo, p.seed_hi, p.n_cdf, p.regular,
-           p.every, p.burst, m.K, m.S, m.seg_ticks, m.tick_offset, m.n_cdf, m.seed_lo, m.seed_hi, (const void *)m.profile,
-           (const void *)a.buf);
+  key_put(key, a.kind, p.seed_lo, p.seed_hi, p.n_cdf, p.regular, p.every, p.burst, m.K, m.S, m.seg_ticks, m.tick_offset, m.n_cdf,
+          m.seed_lo, m.seed_hi, m.profile, a.buf);
 }
 
 // Everything a captured launch sequence bakes into its kernel arguments (a stale graph is never replayed, even when a
-// re-allocated buffer lands on the address the old one had: input_gen)
-void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const void *aobs, const void *areward,
-               const void *adone) {
+// re-allocated buffer lands on the address the old one had: input_gen): the scalars and the caller's outputs, every
+// per-env array of the handle (for_each_env_array), the episode block, the pool's arrays, the stream
+std::string graph_key(tfx_handle h, int n_ticks, int remi, const void *aobs, const void *areward, const void *adone) {
   const Dev &d = h->d;
-  snprintf(key, n, "%llu|%d%d|%ld|%d|%d|%p|%p|%p|%p|%d|%d|%ld|%p|%d|%d|%p|%p|%p|%p|%p|%p|%p|%p|%d.%d.%u.%u|%p|%p|%p|%p|%p|%p",
-           h->input_gen, (int)h->greedy, h->greedy_spacing, d.spawn_stride, n_ticks, remi, aobs, areward, adone, (const void *)d.action,
-           d.action_mode, d.action_period, d.action_stride, (const void *)d.spawn, d.spawn_mode, d.spawn_period, (void *)d.xv,
-           (void *)d.w, (void *)d.obs, (void *)d.rewards, (void *)d.leading, (void *)d.lastcar, (void *)d.waiting,
-           (void *)d.done_tick, h->ep.on, h->ep.max, h->ep.seed_lo, h->ep.seed_hi, (void *)h->ep.ep_return,
-           (void *)h->ep.ep_len, (void *)h->ep.final_return, (void *)h->ep.final_len, (void *)h->ep.trunc,
-           (void *)h->ep.ep_index);
+  static_assert(std::has_unique_object_representations_v<EpDev>, "the key takes the episode block byte for byte");
+  std::string key;
+  key.reserve(1024);
+  key_put(key, h->input_gen, h->greedy, h->greedy_spacing, n_ticks, remi, aobs, areward, adone, d.action, d.action_mode,
+          d.action_period, d.action_stride, d.spawn, d.spawn_mode, d.spawn_period, d.spawn_stride, h->pool);
+  key_put_arrays(key, d);
+  key_put(key, h->ep);  // (no padding: four words, eight pointers)
   // warm restarts (tfx_set_episode_pool): the pool's block is baked into the restart's arguments - whatever of it a
   // caller can re-bind (the rest lives as long as the pool handle does)
   if (const tfx_handle p = h->pool) {
-    const size_t used = strlen(key);
-    const Dev &s = p->d;
-    snprintf(key + used, n - used, "|%p|%p|%p|%p|%p|%p|%p|%p|%p|%p|%p|%p|%d|%p", (void *)p, (void *)s.xv, (void *)s.w,
-             (void *)s.obs, (void *)s.leading, (void *)s.lastcar, (void *)s.rewards, (void *)s.waiting,
-             (void *)s.passed_dst, (void *)s.done_tick, (void *)s.n_trips, (void *)s.trip_times, s.trip_cap,
-             (void *)s.greedy_act);
+    key_put_arrays(key, p->d);
+    key_put(key, p->d.trip_cap, p->d.action_mode, p->d.spawn_mode);
   }
-  const size_t used = strlen(key);
-  stream_key(h->stream, key + used, n - used);
+  stream_key(h->stream, key);
+  return key;
 }
 
 
@@ -71,7 +78,7 @@ void graph_key(tfx_handle h, char *key, size_t n, int n_ticks, int remi, const v
 // no kernel, so what the body added is taken back, kept as the sequence's per-replay addition, and every replay -
 // the first included - adds it again and reports the capture's last mover.
 template <class Body>
-int run_captured(tfx_handle h, CapturedSeq &c, const char *key, hipStream_t st, Body body) {
+int run_captured(tfx_handle h, CapturedSeq &c, const std::string &key, hipStream_t st, Body body) {
   if (!c.exec || c.key != key) {
     if (c.exec) { (void)hipGraphExecDestroy(c.exec); c.exec = nullptr; }
     if (c.graph) { (void)hipGraphDestroy(c.graph); c.graph = nullptr; }
@@ -128,9 +135,7 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
   auto body = [&](hipStream_t s) { return agent_sequence(h, n_ticks, remi, aobs, areward, adone, s, split); };
   if (!capture) return body(st);
   // one graph per distinct launch sequence: everything baked into kernel arguments is in the key
-  char key[1280];
-  graph_key(h, key, sizeof key, n_ticks, remi, aobs, areward, adone);
-  return run_captured(h, h->captured[SEQ_AGENT], key, st, body);
+  return run_captured(h, h->captured[SEQ_AGENT], graph_key(h, n_ticks, remi, aobs, areward, adone), st, body);
 }
 
 namespace {
@@ -280,53 +285,54 @@ int step_body(tfx_handle h, int n_ticks, hipStream_t st) {
   return h->stream.drawn() && n_ticks > 0 ? for_stream_chunks(h, n_ticks, st, ticks) : ticks(n_ticks);
 }
 
-}  // namespace
+// ---- tfx_create's three steps -----------------------------------------------------------------------------
+// the archetype rows a configuration describes: v, l, a, delta, v0, b, T, s0
+struct ArchRows {
+  int n = 1;
+  bool het = false;  // several rows, or an exponent other than 4
+  float row[TFX_MAX_ARCH][8] = {};
+};
 
-extern "C" {
-
-int tfx_abi_version(void) { return TFX_ABI_VERSION; }
-const char *tfx_last_error(void) { return g_err.c_str(); }
-
-int tfx_create(const tfx_config *cfg, tfx_handle *out) {
-  if (!cfg || !out) return fail(TFX_EINVAL, "null argument");
-  if (cfg->m < 1 || cfg->n < 1) return fail(TFX_EINVAL, "grid must be at least 1x1");
-  if (cfg->capacity < 3) return fail(TFX_EINVAL, "capacity must be >= 3 (slot 0 + fake leader + 1 car)");
-  if (cfg->capacity - 2 > 256) return fail(TFX_EINVAL, "capacity-2 > 256 cars per road is not supported");
-  if (cfg->n_envs < 1) return fail(TFX_EINVAL, "n_envs must be >= 1");
-  if (cfg->planes != 2 && cfg->planes != 3) return fail(TFX_EINVAL, "planes must be 2 (x,v) or 3 (x,v,w)");
-  if (cfg->validate && cfg->planes != 3) return fail(TFX_EINVAL, "validate mode needs planes = 3 (spawn tick w)");
-  if (cfg->layout != 0 && cfg->layout != 1) return fail(TFX_EINVAL, "layout must be 0 (ring) or 1 (transposed)");
-  const int n_arch = cfg->n_archetypes <= 1 ? 1 : cfg->n_archetypes;
-  if (n_arch > TFX_MAX_ARCH) return fail(TFX_EINVAL, "at most %d archetype rows", TFX_MAX_ARCH);
-  bool het = n_arch > 1;
-  float arch_rows[TFX_MAX_ARCH][8] = {};
-  for (int a = 0; a < n_arch; ++a) {
-    const float single[8] = {cfg->car_v, cfg->car_l, cfg->car_a, cfg->car_delta, cfg->car_v0, cfg->car_b, cfg->car_T, cfg->car_s0};
-    memcpy(arch_rows[a], cfg->n_archetypes >= 1 ? cfg->arch[a] : single, sizeof single);
-    const float delta = arch_rows[a][3];
+// Step 1: the configuration is one this library runs; its archetype rows
+int check_config(const tfx_config &cfg, ArchRows &ar) {
+  if (cfg.m < 1 || cfg.n < 1) return fail(TFX_EINVAL, "grid must be at least 1x1");
+  if (cfg.capacity < 3) return fail(TFX_EINVAL, "capacity must be >= 3 (slot 0 + fake leader + 1 car)");
+  if (cfg.capacity - 2 > 256) return fail(TFX_EINVAL, "capacity-2 > 256 cars per road is not supported");
+  if (cfg.n_envs < 1) return fail(TFX_EINVAL, "n_envs must be >= 1");
+  if (cfg.planes != 2 && cfg.planes != 3) return fail(TFX_EINVAL, "planes must be 2 (x,v) or 3 (x,v,w)");
+  if (cfg.validate && cfg.planes != 3) return fail(TFX_EINVAL, "validate mode needs planes = 3 (spawn tick w)");
+  if (cfg.layout != 0 && cfg.layout != 1) return fail(TFX_EINVAL, "layout must be 0 (ring) or 1 (transposed)");
+  ar.n = cfg.n_archetypes <= 1 ? 1 : cfg.n_archetypes;
+  if (ar.n > TFX_MAX_ARCH) return fail(TFX_EINVAL, "at most %d archetype rows", TFX_MAX_ARCH);
+  ar.het = ar.n > 1;
+  for (int a = 0; a < ar.n; ++a) {
+    const float single[8] = {cfg.car_v, cfg.car_l, cfg.car_a, cfg.car_delta, cfg.car_v0, cfg.car_b, cfg.car_T, cfg.car_s0};
+    memcpy(ar.row[a], cfg.n_archetypes >= 1 ? cfg.arch[a] : single, sizeof single);
+    const float delta = ar.row[a][3];
     if (!(delta > 0.0f) || !(delta <= 64.0f))
       return fail(TFX_EINVAL, "archetype %d: delta = %g - the exponent must be in (0, 64]", a, delta);
-    if (delta != 4.0f) het = true;
-    if (!(arch_rows[a][2] > 0.0f) || !(arch_rows[a][5] > 0.0f) || !(arch_rows[a][4] > 0.0f))
+    if (delta != 4.0f) ar.het = true;
+    if (!(ar.row[a][2] > 0.0f) || !(ar.row[a][5] > 0.0f) || !(ar.row[a][4] > 0.0f))
       return fail(TFX_EINVAL, "archetype %d: a, b and v0 must be > 0", a);
   }
-  if (het && (cfg->layout != 1 || cfg->planes != 3))
+  if (ar.het && (cfg.layout != 1 || cfg.planes != 3))
     return fail(TFX_EINVAL, "heterogeneous cars (several archetypes, or delta != 4) need layout = 1 and planes = 3");
-  if (!(cfg->length > 0.0f) || !(cfg->rate > 0.0f)) return fail(TFX_EINVAL, "length and rate must be > 0");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(TFX_EDEVICE, "no HIP device");
-  tfx_handle_s *h = new (std::nothrow) tfx_handle_s();
-  if (!h) return fail(TFX_ENOMEM, "out of host memory");
-  h->cfg = *cfg;
-  h->het = het;
-  h->n_arch = n_arch;
-  if (!het && cfg->n_archetypes == 1) {  // one ordinary row given through the table: it IS the archetype
-    h->cfg.car_v = arch_rows[0][0]; h->cfg.car_l = arch_rows[0][1]; h->cfg.car_a = arch_rows[0][2];
-    h->cfg.car_delta = arch_rows[0][3]; h->cfg.car_v0 = arch_rows[0][4]; h->cfg.car_b = arch_rows[0][5];
-    h->cfg.car_T = arch_rows[0][6]; h->cfg.car_s0 = arch_rows[0][7];
-    cfg = &h->cfg;
+  if (!(cfg.length > 0.0f) || !(cfg.rate > 0.0f)) return fail(TFX_EINVAL, "length and rate must be > 0");
+  return TFX_OK;
+}
+
+// Step 2: the host side of the handle - the road tables and storage slots, the environment knobs, the device the handle
+// lives on, the scalars of the device block
+int init_host(tfx_handle_s *h, const tfx_config &given, const ArchRows &ar) {
+  h->cfg = given;
+  h->het = ar.het;
+  h->n_arch = ar.n;
+  if (!ar.het && given.n_archetypes == 1) {  // one ordinary row given through the table: it IS the archetype
+    h->cfg.car_v = ar.row[0][0]; h->cfg.car_l = ar.row[0][1]; h->cfg.car_a = ar.row[0][2];
+    h->cfg.car_delta = ar.row[0][3]; h->cfg.car_v0 = ar.row[0][4]; h->cfg.car_b = ar.row[0][5];
+    h->cfg.car_T = ar.row[0][6]; h->cfg.car_s0 = ar.row[0][7];
   }
+  const tfx_config *cfg = &h->cfg;
   build_tables(h);
   build_slots(h);
   if (const char *mv = getenv("TFX_MOVE_VARIANT")) h->move_variant = atoi(mv);
@@ -365,8 +371,8 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   d.car_v = cfg->car_v; d.car_l = cfg->car_l; d.car_a = cfg->car_a; d.car_v0 = cfg->car_v0;
   d.car_b = cfg->car_b; d.car_T = cfg->car_T; d.car_s0 = cfg->car_s0;
   d.risk_a = cfg->car_a;
-  if (het)
-    for (int a = 0; a < n_arch; ++a) d.risk_a = a == 0 ? arch_rows[0][2] : fmaxf(d.risk_a, arch_rows[a][2]);
+  if (ar.het)
+    for (int a = 0; a < ar.n; ++a) d.risk_a = a == 0 ? ar.row[0][2] : fmaxf(d.risk_a, ar.row[a][2]);
   d.two_sab = 2.0f * sqrtf(cfg->car_a * cfg->car_b);  // 2 * np.sqrt(a*b) (traffic_env.py:54)
   d.eps = cfg->eps;
   d.r_two_sab = 1.0f / d.two_sab;
@@ -374,126 +380,67 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
   d.thresh = cfg->thresh;
   d.near_end = cfg->length - cfg->detect_dist;
   d.ovf_pen = cfg->overflow_penalty;
-  if ((long)d.E * d.R > 0x7fffffffL / 4) { delete h; return fail(TFX_EINVAL, "E*R too large"); }
-
+  if ((long)d.E * d.R > 0x7fffffffL / 4) return fail(TFX_EINVAL, "E*R too large");
+  d.G = h->tiles_per_env;
+  d.trows = d.C - 2;  // (padding the tile stride off the power of two was measured: slightly slower)
+  d.het = ar.het ? 1 : 0;
   const int cars = d.C - 2;
   h->wpr = cars <= 64 ? 1 : (cars <= 128 ? 2 : 4);
+  d.action_mode = TFX_ACTION_CYCLE;
+  d.action_period = 20;
+  d.spawn_mode = TFX_SPAWN_NONE;
+  d.spawn_period = 8;
+  return TFX_OK;
+}
 
-  // tables
+// Step 3: the device side - the road tables, the scratch arena (carve_arena, tfx_dev_layout.hpp: one list sizes it and
+// binds its pointers), the archetype table, the self-tests of the fast paths
+int init_device(tfx_handle_s *h, const ArchRows &ar) {
+  Dev &d = h->d;
   const size_t R = (size_t)d.R;
   const size_t n_slots = h->h_slot_road.size();
-  if (hipMalloc((void **)&h->dev_tables, (4 * R + n_slots) * sizeof(int)) != hipSuccess) {
-    delete h;
+  if (hipMalloc((void **)&h->dev_tables, (4 * R + n_slots) * sizeof(int)) != hipSuccess)
     return fail(TFX_ENOMEM, "hipMalloc(tables) failed");
-  }
   if (hipMemcpy(h->dev_tables, h->h_nexts.data(), R * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->dev_tables + R, h->h_pred.data(), R * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->dev_tables + 2 * R, h->h_entry_idx.data(), R * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->dev_tables + 3 * R, h->h_road_slot.data(), R * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->dev_tables + 4 * R, h->h_slot_road.data(), n_slots * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(h->dev_tables);
-    delete h;
+      hipMemcpy(h->dev_tables + 4 * R, h->h_slot_road.data(), n_slots * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
     return fail(TFX_EDEVICE, "uploading the road tables failed");
-  }
   d.nexts = h->dev_tables;
   d.pred = h->dev_tables + R;
   d.entry_idx = h->dev_tables + 2 * R;
   d.road_slot = h->dev_tables + 3 * R;
   d.slot_road = h->dev_tables + 4 * R;
-  d.G = h->tiles_per_env;
 
-  // scratch
-  const size_t ER = (size_t)d.E * R;
-  size_t off = 0;
-  const size_t o_rec = off;   off = align_up(off + ER * sizeof(int4), 256);
-  const size_t o_rec2 = off;  off = align_up(off + (d.layout == 1 ? ER * sizeof(float2) : 0), 256);
-  const size_t o_rec2c = off; off = align_up(off + (d.layout == 1 ? ER * sizeof(int) : 0), 256);
-  const size_t o_crec = off;  off = align_up(off + (d.layout == 1 ? ER * sizeof(int2) : 0), 256);
-  const size_t o_ovfc = off;  off = align_up(off + (d.layout == 1 ? ER * sizeof(int) : 0), 256);
-  const size_t o_rsw = off;   off = align_up(off + (d.layout == 1 ? ER * sizeof(int) : 0), 256);
-  const size_t o_tail = off;  off = align_up(off + ER * sizeof(float), 256);
-  const size_t o_flag = off;  off = align_up(off + (size_t)d.E * sizeof(int), 256);
-  const size_t o_risk = off;  off = align_up(off + 2 * (size_t)d.E * sizeof(int), 256);
-  d.trows = d.C - 2;  // (padding the tile stride off the power of two was measured: slightly slower)
-  const size_t n_tpairs = (size_t)d.E * d.G * (size_t)d.trows * 64;  // (x, v) pairs of a transposed array
-  // outbox: TFX_KP rows per tile (the cars a road hands over in a tick; round 1 kept a T-sized one)
-  const size_t n_opairs = (size_t)d.E * d.G * KP * 64;
-  const size_t o_outb = off;  off = align_up(off + (d.layout == 1 ? n_opairs * sizeof(float2) : 0), 256);
-  const size_t o_outw = off;  off = align_up(off + (d.layout == 1 && cfg->planes == 3 ? n_opairs * sizeof(float) : 0), 256);
-  const size_t o_lead = off;  off = align_up(off + ER * sizeof(float), 256);
-  const size_t o_taila = off; off = align_up(off + (het ? ER * sizeof(int) : 0), 256);
-  const size_t o_hb = off;    off = align_up(off + (d.layout == 1 ? ER : 0), 256);
-  const size_t o_ep = off;    off = align_up(off + 2 * (size_t)d.E, 256);  // episodes: mark | last (tfx_set_episodes)
-  const size_t o_epd = off;   off = align_up(off + sizeof(EpDev), 256);    // ... and the device copy of the block
-  const size_t o_misc = off;  off = align_up(off + 128, 256);
-  const size_t o_veh = off;   off = align_up(off + (size_t)VEH_SLOTS * VEH_STRIDE * sizeof(unsigned long long), 256);
-  if (hipMalloc(&h->dev_scratch, off) != hipSuccess) {
-    (void)hipFree(h->dev_tables);
-    delete h;
-    return fail(TFX_ENOMEM, "hipMalloc(scratch, %zu bytes) failed", off);
-  }
-  if (hipMemset(h->dev_scratch, 0, off) != hipSuccess) {
-    (void)hipFree(h->dev_tables);
-    (void)hipFree(h->dev_scratch);
-    delete h;
-    return fail(TFX_EDEVICE, "clearing the scratch failed");
-  }
-  char *base = (char *)h->dev_scratch;
-  d.rec = (int4 *)(base + o_rec);
-  d.rec2f = (float2 *)(base + o_rec2);
-  d.rec2c = (int *)(base + o_rec2c);
-  d.crec = d.layout == 1 ? (int2 *)(base + o_crec) : nullptr;
-  d.ovf_cnt = d.layout == 1 ? (int *)(base + o_ovfc) : nullptr;
-  d.rsw = d.layout == 1 ? (int *)(base + o_rsw) : nullptr;
-  d.tailx = (float *)(base + o_tail);
-  d.env_flag = (int *)(base + o_flag);
-  d.env_risk = (int *)(base + o_risk);
-  d.risk_stride = d.E;
-  d.outb = (float2 *)(base + o_outb);
-  d.outw = (float *)(base + o_outw);
-  d.leadx = (float *)(base + o_lead);
-  d.hb = d.layout == 1 ? (uint8_t *)(base + o_hb) : nullptr;
-  d.het = het ? 1 : 0;
-  d.taila = (int *)(base + o_taila);
-  h->ep.mark = (uint8_t *)(base + o_ep);
-  h->ep.last = h->ep.mark + d.E;
-  h->dev_ep = (EpDev *)(base + o_epd);
-  if (het) {
+  // the scratch arena: sized, allocated and cleared, bound
+  const size_t bytes = carve_arena(d, h->ep, h->dev_ep, h->misc, h->cfg.planes, nullptr);
+  if (hipMalloc(&h->dev_scratch, bytes) != hipSuccess) return fail(TFX_ENOMEM, "hipMalloc(scratch, %zu bytes) failed", bytes);
+  if (hipMemset(h->dev_scratch, 0, bytes) != hipSuccess) return fail(TFX_EDEVICE, "clearing the scratch failed");
+  carve_arena(d, h->ep, h->dev_ep, h->misc, h->cfg.planes, (char *)h->dev_scratch);
+  if (ar.het) {
     float tab[TFX_MAX_ARCH][ARCH_W] = {};
-    for (int a = 0; a < n_arch; ++a) {
-      const float *r = arch_rows[a];  // v, l, a, delta, v0, b, T, s0
+    for (int a = 0; a < ar.n; ++a) {
+      const float *r = ar.row[a];
       tab[a][AR_L] = r[1]; tab[a][AR_A] = r[2]; tab[a][AR_V0] = r[4]; tab[a][AR_T] = r[6]; tab[a][AR_S0] = r[7];
       tab[a][AR_2SAB] = 2.0f * sqrtf(r[2] * r[5]);  // 2 * np.sqrt(a*b) (traffic_env.py:54)
       tab[a][AR_DELTA] = r[3]; tab[a][AR_V] = r[0];
     }
     if (hipMalloc((void **)&h->dev_arch, sizeof tab) != hipSuccess ||
-        hipMemcpy(h->dev_arch, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(h->dev_tables);
-      (void)hipFree(h->dev_scratch);
-      delete h;
+        hipMemcpy(h->dev_arch, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess)
       return fail(TFX_ENOMEM, "uploading the archetype table failed");
-    }
     d.arch_tab = h->dev_arch;
   }
-  h->n_tpairs = n_tpairs;
-  d.veh = (unsigned long long *)(base + o_veh);
-  d.tickA = (int *)(base + o_misc + 16);
-  d.tickB = (int *)(base + o_misc + 32);
-  d.agent_first = (const int *)(base + o_misc + 48);
-  d.risk_any = (int *)(base + o_misc + 56);   // two words
-  d.slow_pairs = (unsigned long long *)(base + o_misc + 88);
-  h->tick2 = (int *)(base + o_misc + 64);     // tickA, tickB, risk_any[2] of the second half
-  h->clone_skipped = (unsigned long long *)(base + o_misc + 96);
   // reciprocal division is used only if it is exact for this handle's constants on the whole
   // admitted numerator domain (2 x ~2^31 quotients, a few milliseconds; TFX_FASTDIV=0 disables)
   d.fastdiv = 0;
   {
     const char *fd = getenv("TFX_FASTDIV");
     if (!fd || atoi(fd) != 0) {
-      unsigned long long *bad = (unsigned long long *)(base + o_misc);  // scratch word, zero at this point
+      unsigned long long *bad = &h->misc->selftest;  // zero at this point
       hipLaunchKernelGGL(k_div_selftest, dim3(h->n_cu * 8), dim3(256), 0, 0, d.two_sab, d.r_two_sab,
                          TFX_FASTDIV_A_LO, TFX_FASTDIV_A_HI, bad);
-      hipLaunchKernelGGL(k_div_selftest, dim3(h->n_cu * 8), dim3(256), 0, 0, cfg->car_v0, d.r_v0,
+      hipLaunchKernelGGL(k_div_selftest, dim3(h->n_cu * 8), dim3(256), 0, 0, h->cfg.car_v0, d.r_v0,
                          TFX_FASTDIV_V_LO, TFX_FASTDIV_V_HI, bad);
       unsigned long long nbad = 1;
       if (hipMemcpy(&nbad, bad, sizeof nbad, hipMemcpyDeviceToHost) == hipSuccess && nbad == 0) d.fastdiv = 1;
@@ -502,17 +449,36 @@ int tfx_create(const tfx_config *cfg, tfx_handle *out) {
     }
   }
   {
-    unsigned *bad = (unsigned *)(base + o_misc);  // (cleared again above)
+    unsigned *bad = reinterpret_cast<unsigned *>(&h->misc->selftest);  // (cleared again above)
     hipLaunchKernelGGL(k_max_selftest, dim3(1), dim3(1), 0, 0, bad, 0.0f, -0.0f);
     unsigned nbad = 1;
     if (hipMemcpy(&nbad, bad, sizeof nbad, hipMemcpyDeviceToHost) == hipSuccess && nbad == 0) d.fastmax = 1;
     (void)hipMemset(bad, 0, 8);
   }
-  d.action_mode = TFX_ACTION_CYCLE;
-  d.action_period = 20;
-  d.spawn_mode = TFX_SPAWN_NONE;
-  d.spawn_period = 8;
-  *out = h;
+  return TFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tfx_abi_version(void) { return TFX_ABI_VERSION; }
+const char *tfx_last_error(void) { return g_err.c_str(); }
+
+int tfx_create(const tfx_config *cfg, tfx_handle *out) {
+  if (!cfg || !out) return fail(TFX_EINVAL, "null argument");
+  ArchRows ar;
+  if (int rc = check_config(*cfg, ar)) return rc;
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (ndev < 1) return fail(TFX_EDEVICE, "no HIP device");
+  // the half-built handle is released through tfx_destroy, which tolerates every member being null: a failure below
+  // is a plain return
+  std::unique_ptr<tfx_handle_s, int (*)(tfx_handle)> h(new (std::nothrow) tfx_handle_s(), tfx_destroy);
+  if (!h) return fail(TFX_ENOMEM, "out of host memory");
+  if (int rc = init_host(h.get(), *cfg, ar)) return rc;
+  if (int rc = init_device(h.get(), ar)) return rc;
+  *out = h.release();
   return TFX_OK;
 }
 
@@ -572,7 +538,7 @@ int tfx_bind_buffers(tfx_handle h, const tfx_buffers *b) {
   Dev &d = h->d;
   d.xv = reinterpret_cast<float2 *>(b->xv); d.w = b->w;
   d.leading = b->leading; d.lastcar = b->lastcar; d.obs = b->obs;
-  d.lights = b->obs + 2 * d.r; d.lights_stride = d.obs_len;
+  d.lights = env_lights(d); d.lights_stride = d.obs_len;
   d.rewards = b->rewards; d.waiting = b->waiting; d.passed_dst = b->passed_dst;
   d.done_tick = b->done_tick; d.trip_times = b->trip_times; d.n_trips = b->n_trips;
   d.trip_cap = b->trip_cap;
@@ -823,9 +789,7 @@ int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
   auto body = [&](hipStream_t s) { return step_body(h, n_ticks, s); };
   if (!capture) return body(st);
   // captured once per distinct sequence (graph_key), replayed afterwards
-  char key[1280];
-  graph_key(h, key, sizeof key, n_ticks, -1, nullptr, nullptr, nullptr);
-  return run_captured(h, h->captured[SEQ_STEP], key, st, body);
+  return run_captured(h, h->captured[SEQ_STEP], graph_key(h, n_ticks, -1, nullptr, nullptr, nullptr), st, body);
 }
 
 int tfx_move_cars(tfx_handle h, void *stream) {
@@ -944,7 +908,7 @@ int tfx_profile_read(tfx_handle h, double *move_ms, double *advance_ms, int32_t 
 int tfx_xv_pairs(tfx_handle h, int64_t *pairs) {
   if (int rc = check_handle(h, false)) return rc;
   if (!pairs) return fail(TFX_EINVAL, "pairs is null");
-  *pairs = h->d.layout == 1 ? (int64_t)h->n_tpairs : (int64_t)h->d.E * h->d.R * h->d.C;
+  *pairs = (int64_t)h->d.E * (int64_t)env_car_pairs(h->d);
   return TFX_OK;
 }
 
@@ -1088,7 +1052,7 @@ int tfx_clone_envs(tfx_handle dst, tfx_handle src, const int32_t *src_of_env, in
   }
   CloneOpt o{};
   o.same = dst == src ? 1 : 0;
-  o.skipped = dst->clone_skipped;
+  o.skipped = &dst->misc->clone_skipped;
   if (flags & TFX_CLONE_STREAM) {
     if (int rc = streams_compatible(dst, src)) return rc;
     const ArrivalStream &p = dst->stream, &q = src->stream;
@@ -1137,8 +1101,8 @@ int tfx_clone_skipped(tfx_handle h, uint64_t *skipped, void *stream) {
   if (!skipped) return fail(TFX_EINVAL, "skipped is null");
   // read and cleared ON the stream, behind the clones enqueued there and ahead of the next one
   unsigned long long v = 0;
-  HIPCHK(hipMemcpyAsync(&v, h->clone_skipped, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipMemsetAsync(h->clone_skipped, 0, sizeof v, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(&v, &h->misc->clone_skipped, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemsetAsync(&h->misc->clone_skipped, 0, sizeof v, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   *skipped = (uint64_t)v;
   return TFX_OK;

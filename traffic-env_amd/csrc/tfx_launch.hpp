@@ -9,7 +9,8 @@
 //           uses it first.
 //   launch  the launch_* functions launch what the pick names with the grid the handle holds, and note the mover in
 //           step_kernel; they size nothing.
-// (k_res is sized when the buffers are bound: res_configure.)
+// (k_res is sized when the buffers are bound: res_configure.  The envs of one half of a split call as a Dev of their
+// own: sub_dev, tfx_dev_layout.hpp.)
 #pragma once
 #include <map>
 
@@ -99,7 +100,7 @@ Pick<TickFn> pick_move_t(const tfx_handle_s *h) {
   // 0.0365 vs 0.0392 ms, x 256 0.048 vs 0.054, x 384 0.068 vs 0.080, x 512 (286 MB) 0.086 vs 0.093,
   // cfg4 x 16 (272 MB) 0.096 vs 0.103, x 24 (409 MB) 0.134 vs 0.150; at cfg2 x 1024 (573 MB) it is the
   // other way round: 0.199 vs 0.173.  (12 or 16 rows in flight, or 8 resident blocks per CU: no better.)
-  if (pvar == 0 && h->n_tpairs * sizeof(float2) <= (size_t)448 << 20) return t(k_move_t<8>);
+  if (pvar == 0 && (size_t)h->d.E * env_car_pairs(h->d) * sizeof(float2) <= (size_t)448 << 20) return t(k_move_t<8>);
   // beyond that every row is read once and written once per tick: non-temporal loads AND stores (0.82 -> 0.70 ms
   // at cfg2, and the following k_advance no longer waits for dirty lines: 0.057 -> 0.032 ms)
   return t(k_move_t<4, 3>);
@@ -481,55 +482,6 @@ Pick<TickFn> pick_tts(int S, bool w, bool agent, bool crec, bool rsw) {
   if (S == 8) return w ? tts_form<8, true>(agent, crec, rsw) : tts_form<8, false>(agent, crec, rsw);
   if (S == 4) return w ? tts_form<4, true>(agent, crec, rsw) : tts_form<4, false>(agent, crec, rsw);
   return w ? tts_form<2, true>(agent, crec, rsw) : tts_form<2, false>(agent, crec, rsw);
-}
-
-// The envs [lo, lo + n) of a handle as a Dev of their own: every per-env array starts at env lo, the global env
-// id offset moves along (on-device rules are functions of the global id), the vehicle-update counter is shared.
-Dev sub_dev(const tfx_handle_s *h, int lo, int n, int *clock) {
-  Dev s = h->d;
-  const Dev &d = h->d;
-  const size_t R = (size_t)d.R, I = (size_t)d.I, r = (size_t)d.r, L = (size_t)lo;
-  s.E = n;
-  s.env_off = d.env_off + lo;
-  const size_t tile_pairs = (size_t)d.G * (size_t)d.trows * 64, out_pairs = (size_t)d.G * KP * 64;
-  s.xv = d.xv + L * (d.layout == 1 ? tile_pairs : R * d.C);
-  if (d.w) s.w = d.w + L * (d.layout == 1 ? tile_pairs : R * d.C);
-  s.leading = d.leading + L * R;
-  s.lastcar = d.lastcar + L * R;
-  s.obs = d.obs + L * (size_t)d.obs_len;
-  s.lights = s.obs + 2 * d.r;
-  s.rewards = d.rewards + L * I;
-  s.waiting = d.waiting + L * r;
-  s.passed_dst = d.passed_dst + L * I;
-  s.done_tick = d.done_tick + L;
-  if (d.trip_times) s.trip_times = d.trip_times + L * (size_t)d.trip_cap;
-  if (d.n_trips) s.n_trips = d.n_trips + L;
-  s.rec = d.rec + L * R;
-  s.rec2f = d.rec2f + L * R;
-  if (d.rsw) s.rsw = d.rsw + L * R;
-  if (d.crec) {
-    s.crec = d.crec + L * R;
-    s.ovf_cnt = d.ovf_cnt + L * R;
-  }
-  s.rec2c = d.rec2c + L * R;
-  if (d.hb) s.hb = d.hb + L * R;
-  s.tailx = d.tailx + L * R;
-  if (d.taila) s.taila = d.taila + L * R;
-  if (d.spawn_arch) s.spawn_arch = d.spawn_arch + L * (size_t)d.n_entry * (size_t)d.spawn_arch_S;
-  s.leadx = d.leadx + L * R;
-  s.outb = d.outb + L * out_pairs;
-  if (d.outw) s.outw = d.outw + L * out_pairs;
-  s.env_flag = d.env_flag + L;
-  s.env_risk = d.env_risk + L;
-  if (d.action_mode == TFX_ACTION_BUFFER && d.action) s.action = d.action + L * I;
-  if (d.greedy_act) s.greedy_act = d.greedy_act + L * I;
-  if (d.spawn_mode == TFX_SPAWN_COUNTS && d.spawn) s.spawn = d.spawn + L * (size_t)d.n_entry;
-  if (clock) {
-    s.tickA = clock;
-    s.tickB = clock + 1;
-    s.risk_any = clock + 2;
-  }
-  return s;
 }
 
 // k_tail (tfx_tail.hpp) replaces k_advance(t) k_edge(t+1) k_advance(t+1) behind a two-tick pass: one workgroup per

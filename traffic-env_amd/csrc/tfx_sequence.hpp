@@ -190,12 +190,12 @@ int run_ticks(tfx_handle h, int n_ticks, hipStream_t st, bool agent, bool split)
     // (the second half's clock is copied on the CALLER's stream, ahead of the fork: copied on the second stream it
     // raced with the first half's kernels, which move the clock on - a new stream's first launch can take longer to
     // start than a small batch's whole pair)
-    hipLaunchKernelGGL(k_clock_copy, dim3(1), dim3(1), 0, st, whole.tickA, whole.tickB, h->tick2);
+    hipLaunchKernelGGL(k_clock_copy, dim3(1), dim3(1), 0, st, whole.tickA, whole.tickB, h->misc->clock2);
     HIPCHK(hipGetLastError());
     if (int rc = guard.fork(st)) return rc;
     const int n0 = whole.E / 2;
-    halves[0] = sub_dev(h, 0, n0, nullptr);
-    halves[1] = sub_dev(h, n0, whole.E - n0, h->tick2);
+    halves[0] = sub_dev(whole, 0, n0, nullptr);
+    halves[1] = sub_dev(whole, n0, whole.E - n0, h->misc->clock2);
   }
   // The two halves' launches are submitted pair by pair, alternately.  (Submitted half after half - all of the first
   // half's launches, then the second's - the second stream's first launch reached the device only after the host had
