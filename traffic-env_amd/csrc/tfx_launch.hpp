@@ -670,8 +670,11 @@ int launch_move_tt(tfx_handle h, bool two, bool agent, int tidx, hipStream_t st,
     h->step_kernel = p.name;
     rc = launch(h, p, grid, st, tidx);
   } else {
-    // 16 workgroups per CU for the 6 resident ones size_grids found (see there), never more than there is work
-    long grid = (long)h->grid_tt[(two ? 1 : 0) + (agent ? 2 : 0)] * 16 / 6;
+    // 16 workgroups per CU for the 6 resident ones size_grids found (see there), never more than there is work; 18 for
+    // the plain two-tick pass at seven wavefronts per SIMD (measured at cfg2, split call, 14 / 16 / 17 / 18 / 19 / 20 / 21 /
+    // 24 per CU: 0.3806 / 0.3772 / 0.3773 / 0.3736-0.3749 / 0.3731 / 0.3818 / 0.3789 / 0.3802 ms per tick)
+    const int per_six = (TT_WAVES == 7 && two && !agent && !d.w) ? 18 : 16;
+    long grid = (long)h->grid_tt[(two ? 1 : 0) + (agent ? 2 : 0)] * per_six / 6;
     if (h->move_blocks_per_cu > 0) grid = (long)h->move_blocks_per_cu * h->n_cu;
     const long need = (tiles + 3) / 4;
     if (grid > need) grid = need;

@@ -52,11 +52,24 @@ namespace tfx {
 #ifndef TT_P
 #define TT_P 4
 #endif
-// Six wavefronts per SIMD (<= 80 vector registers).  Measured at cfg2 (ms per pass, alone on the chip / vehicle-updates
-// per second of the split call): 5 per SIMD (81 registers, what the compiler picks) 0.764 / 4.92e11, 6: 0.745 / 5.22e11,
-// 7: 0.728 / 5.04e11, 8: 0.746 / 4.98e11 - at 6 the pass leaves room for one k_tail wavefront per SIMD beside it.
+// Seven wavefronts per SIMD (<= 72 vector registers) for the plain forms, which fit them without scratch since the walk
+// addresses its rows as a wave-uniform base plus ONE 32-bit offset per lane (left alone the compiler takes 71-74
+// registers; tests/test_pass_registers.py holds the line).  Measured at cfg2, pass / k_tail wavefronts per SIMD -> ms per
+// tick of the split call, interleaved on one box (profiles/r05_pass_registers.txt): the parent's 6 / 6 with
+// two dwords of scratch 0.3844-0.3866, 6 / 6 clean 0.3825-0.3840, 7 / 7 0.3772-0.3782 (0.3707-0.3739 with 18 workgroups
+// per CU, launch_move_tt), 7 / 6 0.4065-0.4070, 6 / 7 0.4011-0.4019.  What pays is not the seventh wavefront of the pass -
+// alone on the chip a launch takes 0.705 ms either way - but that a k_tail wavefront of the other half fits wherever a
+// pass wavefront does, seven to a SIMD in any mixture; with unequal sizes k_tail waits for slots.
+// (Before the diet, with spills, ms per pass / vehicle-updates per second of the split call: 5 per SIMD 0.764 / 4.92e11,
+// 6: 0.745 / 5.22e11, 7: 0.728 / 5.04e11, 8: 0.746 / 4.98e11.)
 #ifndef TT_WAVES
-#define TT_WAVES 6
+#define TT_WAVES 7
+#endif
+// Inside agent steps both kernels keep six (<= 80 registers): k_tail<AGENT> spills 68 bytes at 72 against 28 at 80, and
+// seven bought a fused decision nothing (4.53-4.54 ms at 7 / 7, 4.62-4.64 at 6 / 6 in another session; the parent's walk
+// took 4.40-4.47 - the agent form lost 3.6 % per launch with the diet, cause not found: DESIGN.md 6).
+#ifndef TT_WAVES_AGENT
+#define TT_WAVES_AGENT 6
 #endif
 // With the side-word plane (validate mode, heterogeneous cars): five per SIMD (<= 96 registers; the kernels would take
 // 105-128).  Measured at cfg2, ms per tick of the split call at 4 / 5 / 6 per SIMD: validate mode 0.637 / 0.602 / 0.597,
@@ -64,7 +77,13 @@ namespace tfx {
 #ifndef TT_WAVES_W
 #define TT_WAVES_W 5
 #endif
-#define TT_ATTR(W) __attribute__((amdgpu_waves_per_eu((W) ? TT_WAVES_W : TT_WAVES, (W) ? TT_WAVES_W : TT_WAVES)))
+// k_tail of a plain call, which runs beside the pass of the other half: the registers of one wavefront of the pass (it
+// spills 24 bytes at 72 and takes 140.5 us per launch against 137.3 - the pairing above pays for that many times over)
+#ifndef TT_WAVES_TAIL
+#define TT_WAVES_TAIL TT_WAVES
+#endif
+#define TT_ATTR_N(W, N) __attribute__((amdgpu_waves_per_eu((W) ? TT_WAVES_W : (N), (W) ? TT_WAVES_W : (N))))
+#define TT_ATTR(W, AGENT) TT_ATTR_N(W, (AGENT) ? TT_WAVES_AGENT : TT_WAVES)
 // W: the spawn-tick plane travels with the cars (validate mode, advance_hack's trip times :139-157): a car's side word
 // is stored wherever its (x, v) is
 // HET (implies W): heterogeneous cars, as in k_move_t - the side word is 8 * spawn tick + the car's row of the archetype
@@ -96,10 +115,16 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   const int n_old = run ? p.n_old : 0;
   const int n_sp = run ? p.n_tot - p.n_old : 0;
 
-  float2 *col = d.xv + ((size_t)tile * d.trows) * 64 + lane;  // written: row k of this road = col[k * 64]
-  const float2 *colr = col + (size_t)hb * 64;                 // read: the live rows start hb rows down
-  float2 *ocol = d.outb + ((size_t)tile * KP) * 64 + lane;
-  float *wcol = W ? d.w + ((size_t)tile * d.trows) * 64 + lane : nullptr;  // side words: same rows as col
+  // Addresses: one wave-uniform base per tile plus a 32-bit byte offset per lane (a column is at most 256 rows of 512
+  // bytes), not a 64-bit pointer per lane for each of the rows read, the rows written and the outbox.
+  char *const tb = reinterpret_cast<char *>(d.xv + ((size_t)tile * d.trows) * 64);  // row k of this road: tb + k * 512 + lo
+  char *const ox = reinterpret_cast<char *>(d.outb + ((size_t)tile * KP) * 64);
+  const unsigned lo = (unsigned)lane * 8u;
+  const unsigned ro = lo + (unsigned)hb * 512u;  // read: the live rows start hb rows down
+  auto row_at = [&](char *base, unsigned k, unsigned off) {  // (all of the per-lane part in ONE 32-bit register)
+    return reinterpret_cast<float2 *>(base + (size_t)(k * 512u + off));
+  };
+  float *wcol = W ? d.w + ((size_t)tile * d.trows) * 64 + lane : nullptr;  // side words: same rows as the cars
   float *owcol = W ? d.outw + ((size_t)tile * KP) * 64 + lane : nullptr;
 
   int kmax = n_old;
@@ -115,10 +140,13 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   float y1w = 0.0f;                                      // side word of car k-1
   float y1l = 0.0f, y2l = 0.0f;                          // HET: lengths of cars k-1 and k-2
   int last_a = 0;                                        // HET: table row of the last car processed (the road's tail)
-  int kpop = 0, n_wait = 0, n_det = 0, n_wait1 = 0, n_det1 = 0;
+  // Counts of the walk.  The waiting cars of both ticks are only ever used as their sum (rec2c; a tile that takes one
+  // tick counts none of the second), and the two `detected` counts (<= 256 each) share a word: tick t in the low half,
+  // tick t+1 in the high half.
+  int kpop = 0, n_wait = 0, n_det2 = 0;
   bool open = true, far = false;
   bool pend = false, pend_int = false;  // car k-1 survived tick t and is still to be stored; it is not the new head
-  float2 *wp = col;  // where the next surviving car goes: one row further down per survivor
+  unsigned wo = lo;  // where the next surviving car goes (byte offset from tb): one row further down per survivor
   int kq1 = 0x7fffffff;  // tick t+1 tests x instead of v from this car on (index of tick t)
   float tail_x = 0.0f, tail_z = 0.0f;
   const int kq = (p.ld > p.lc) ? C - 1 - p.ld : 0x7fffffff;
@@ -159,13 +187,13 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
       if (TWO) idm_step(d, y1x, y1v, y2x, y2v, d.car_l, zx, zv);
     }
     if (TWO && two && pend) {  // car k-1: the new head keeps its tick-t state (k_edge moves it), the others are a tick ahead
-      st2(wp, pend_int ? zx : y1x, pend_int ? zv : y1v);
-      if (W) wcol[wp - col] = y1w;
-      wp += 64;
+      st2(row_at(tb, 0, wo), pend_int ? zx : y1x, pend_int ? zv : y1v);
+      if (W) wcol[(wo - lo) >> 3] = y1w;
+      wo += 512u;
       if (pend_int) {
         const float wq1 = (k - 1 >= kq1) ? zx : zv;
-        n_wait1 += (wq1 < d.thresh) ? 1 : 0;
-        n_det1 += (zx > d.near_end) ? 1 : 0;
+        n_wait += (wq1 < d.thresh) ? 1 : 0;
+        n_det2 += (zx > d.near_end) ? 0x10000 : 0;
         if (LAST) tail_z = zx;  // (the road's last car is flushed by the LAST call)
       }
     }
@@ -178,27 +206,27 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
     open = pop;
     if (pop) {
       if (kpop < KP) {
-        ocol[(size_t)kpop * 64] = make_float2(xn, vn);
+        *row_at(ox, 0, lo + (unsigned)kpop * 512u) = make_float2(xn, vn);
         if (W) owcol[(size_t)kpop * 64] = sw;
       } else {  // third pop: no survivor has been written yet - from here on every car stays in its row
-        st2(&col[(size_t)k * 64], xn, vn);
+        st2(row_at(tb, (unsigned)k, lo), xn, vn);
         if (W) wcol[(size_t)k * 64] = sw;
-        wp = col + (size_t)(k + 1) * 64;
+        wo = lo + (unsigned)(k + 1) * 512u;
       }
       far = far || ((xn - d.length) > d.length);
-      ++kpop;
     } else if (TWO && two) {
       pend = true;
       pend_int = !was_open;
       if (was_open) kq1 = C - 1 - ring_adv(p.ld, kpop, C) + kpop;  // (kpop is final: this is the first survivor)
     } else {
-      st2(wp, xn, vn);
-      if (W) wcol[wp - col] = sw;
-      wp += 64;
+      st2(row_at(tb, 0, wo), xn, vn);
+      if (W) wcol[(wo - lo) >> 3] = sw;
+      wo += 512u;
     }
+    kpop += pop ? 1 : 0;  // (after the branches: they use the pops BEFORE this car)
     const float wq = (k >= kq) ? xn : vn;
     n_wait += (wq < d.thresh) ? 1 : 0;
-    n_det += (xn > d.near_end) ? 1 : 0;
+    n_det2 += (xn > d.near_end) ? 1 : 0;
     if (!TWO) tail_x = xn;  // (a pair: y1 holds the last car's new state when the walk ends)
     y2x = y1x;
     y2v = y1v;
@@ -217,7 +245,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   const float *wcolr = wcol + (size_t)hb * 64;
 #pragma unroll
   for (int u = 0; u < P; ++u) {
-    pf[u] = (u < n_old) ? ld2(&colr[(size_t)u * 64]) : make_float2(0.0f, 0.0f);
+    pf[u] = (u < n_old) ? ld2(row_at(tb, (unsigned)u, ro)) : make_float2(0.0f, 0.0f);
     pfw[u] = (W && u < n_old) ? wcolr[(size_t)u * 64] : 0.0f;
   }
   for (int k0 = 0; k0 < kmax; k0 += P) {
@@ -228,7 +256,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
         const float2 cur = pf[u];
         const float curw = pfw[u];
         if (k + P < kmax) {
-          pf[u] = (k + P < n_old) ? ld2(&colr[(size_t)(k + P) * 64]) : make_float2(0.0f, 0.0f);
+          pf[u] = (k + P < n_old) ? ld2(row_at(tb, (unsigned)(k + P), ro)) : make_float2(0.0f, 0.0f);
           pfw[u] = (W && k + P < n_old) ? wcolr[(size_t)(k + P) * 64] : 0.0f;
         }
         if (k < n_old) step(k, cur.x, cur.y, curw, std::false_type{});
@@ -278,6 +306,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   // ---- phase W -------------------------------------------------------------------------------
   if (run) {
     const int n_tot = p.n_tot;
+    const int n_det = n_det2 & 0xffff, n_det1 = n_det2 >> 16;
     if (e < d.r) {
       int *ob = d.obs + (size_t)env * d.obs_len;
       if (n_tot > 0 && !two) {  // (a pair: edge_tile adds both ticks' waiting counts at once and stores `detected` -
@@ -299,7 +328,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
     }
     if (two) {
       d.rec2f[id] = make_float2(y1v, tail_z);
-      d.rec2c[id] = rec2c_pack(n_wait + n_wait1, n_det1, n_det, n_tot > 0);
+      d.rec2c[id] = rec2c_pack(n_wait, n_det1, n_det, n_tot > 0);
     }
     if (far || kpop > KP) d.env_flag[env] = tick + 1;
     if (!two) d.leadx[id] = p.xL;  // (read by tfx_export_ring only: the second tick of a pair writes its own)
@@ -309,7 +338,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
 }
 
 template <bool TWO, bool AGENT = false, bool W = false, bool HET = false, bool CREC = false, bool RSW = false>
-__global__ __launch_bounds__(256) TT_ATTR(W) void k_move_tt(const Dev d, const int tidx, const int only_risky) {
+__global__ __launch_bounds__(256) TT_ATTR(W, AGENT) void k_move_tt(const Dev d, const int tidx, const int only_risky) {
   static_assert(!CREC || TWO, "only a two-tick pass is followed by k_tail");
   static_assert(!RSW || (CREC && !AGENT && !HET), "road state words: between the pairs of a plain tfx_step call");
   static_assert(!HET || W, "heterogeneous cars carry their table row in the side word");

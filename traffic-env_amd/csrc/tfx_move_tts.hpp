@@ -22,6 +22,11 @@
 #pragma once
 #include "tfx_move_tt.hpp"
 
+// the segmented pass keeps six wavefronts per SIMD whatever the whole-column pass takes (its walk is its own)
+#ifndef TT_WAVES_S
+#define TT_WAVES_S 6
+#endif
+
 namespace tfx {
 
 constexpr int TTS_HOLD = KP + 3;
@@ -345,7 +350,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
 // a workgroup = TPW tiles x S segments (S = 2: two tiles; 4, 8: one)
 template <bool AGENT, bool CREC, bool RSW, int S, bool W = false>
 __global__ __launch_bounds__(S == 2 ? 256 : 64 * S)
-__attribute__((amdgpu_waves_per_eu(S == 2 ? (W ? TT_WAVES_W : TT_WAVES) : 4, S == 2 ? (W ? TT_WAVES_W : TT_WAVES) : 4)))
+__attribute__((amdgpu_waves_per_eu(S == 2 ? (W ? TT_WAVES_W : TT_WAVES_S) : 4, S == 2 ? (W ? TT_WAVES_W : TT_WAVES_S) : 4)))
 void k_move_tts(const Dev d, const int tidx) {
   static_assert(!RSW || (CREC && !AGENT), "road state words: between the pairs of a plain tfx_step call");
   constexpr int TPW = S == 2 ? 2 : 1;
