@@ -71,7 +71,7 @@ def load_random(eng, seed):
 # ---- 1. synthetic states through the ring import -----------------------------------------------------------------------
 @pytest.mark.parametrize("path,kind", [("pertick", "plain"), ("pertick", "validate"), ("pertick", "het"),
                                        ("ring", "plain"), ("ring", "validate")])
-@pytest.mark.parametrize("capacity", [14, 66])          # 66: road counts 0 .. 64 straddle every multiple of MEAS_P = 8
+@pytest.mark.parametrize("capacity", [14, 66])          # 66: road counts 0 .. 64 straddle every multiple of WALK_P = 8
 @pytest.mark.parametrize("m,n", [(3, 3), (4, 4)])        # 48 roads: one partial tile; 80: a full tile and 16 lanes of a second
 def test_synthetic_states(path, kind, capacity, m, n):
     eng = make(path, 5, kind, m=m, n=n, capacity=capacity)

@@ -60,7 +60,7 @@ def zeros_like_stats(eng, n_bins):
 
 # ---- 1. synthetic ages through the ring import ----------------------------------------------------------------------------
 @pytest.mark.parametrize("path,kind", [("pertick", "validate"), ("pertick", "het"), ("ring", "validate")])
-@pytest.mark.parametrize("capacity", [14, 66])          # 66: road counts 0 .. 64 straddle every multiple of MEAS_P = 8
+@pytest.mark.parametrize("capacity", [14, 66])          # 66: road counts 0 .. 64 straddle every multiple of WALK_P = 8
 @pytest.mark.parametrize("m,n", [(3, 3), (4, 4)])        # 48 roads: one partial tile; 80: a full tile and 16 lanes of a second
 def test_synthetic_ages(path, kind, capacity, m, n):
     eng = make(path, 5, kind, m=m, n=n, capacity=capacity)

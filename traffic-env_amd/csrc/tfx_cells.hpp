@@ -1,9 +1,7 @@
 // tfx_cells.hpp - k_cells: car count and speed sum per CELL of every road (tfx_road_cells, include/tfx.h) - the discrete
 // traffic state encoding - from ONE read of the live cars.  k_measure (tfx_measure.hpp) generalised from four words per
-// road to B cells per road; read-only like it, and with its decomposition: a wavefront per (env, tile), four to a
-// workgroup, lane per road through slot_road, a stride loop over the E * G items, the tile's deepest live row reduced
-// across the wavefront, rows walked as coalesced 512-byte loads with CELL_P rows in flight, a lane loading only rows
-// hb .. hb + n - 1 of its own column.  Ring layout: each lane walks the ring slots of its road with wrap1.
+// road to B cells per road; read-only like it, and on the same walk (tfx_walk.hpp) in its uniform form: every lane takes
+// part in every step up to the tile's longest road, because a step uses ballot and cross-lane reads.
 //
 // What is new:
 //   * B running values per lane cannot be registers (a dynamically indexed register array goes to scratch).  The two
@@ -24,11 +22,9 @@
 // Instantiated on the cell bound (8, 16, 32: 16, 32, 64 KB of LDS per workgroup), so that few cells keep their occupancy.
 #pragma once
 #include "tfx_common.hpp"
-#include "tfx_move_t.hpp"
+#include "tfx_walk.hpp"
 
 namespace tfx {
-
-constexpr int CELL_P = 8;  // rows in flight per wavefront
 
 struct CellEdges {
   float lo, hi;                  // edges[0], edges[B]: in range iff lo <= x < hi
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256) void k_cells(const Dev d, const CellEdges ed, 
   __shared__ float s_sum[4][BMAX * 64];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int G = d.G, R = d.R, C = d.C;
+  const int G = d.G, R = d.R;
   const long items = (long)d.E * G;
   const long nw = (long)gridDim.x * 4;
   const bool want_n = o.n_cars != nullptr, want_s = o.speed_sum != nullptr;
@@ -109,13 +105,8 @@ __global__ __launch_bounds__(256) void k_cells(const Dev d, const CellEdges ed, 
 
   for (long item = (long)blockIdx.x * 4 + wv; item < items; item += nw) {
     const int env = (int)(item / G);
-    const int g = (int)(item - (long)env * G);
-    const int e_slot = d.slot_road[g * 64 + lane];
-    const bool valid = e_slot >= 0;
-    const size_t id = (size_t)env * R + (valid ? e_slot : 0);
-    const int ld = d.leading[id];
-    int n = valid ? ring_count(ld, d.lastcar[id], C) : 0;
-    n = n < 0 ? 0 : (n > C - 1 ? C - 1 : n);
+    const TileRoad r = tile_road(d, env, (int)(item - (long)env * G), lane);
+    const int e_slot = r.e_slot;
 
     CellWalk<BMAX> w{s_cnt[wv], s_sum[wv], lane, edge, want_n, want_s};
     for (int b = 0; b < B; ++b) {
@@ -123,48 +114,7 @@ __global__ __launch_bounds__(256) void k_cells(const Dev d, const CellEdges ed, 
       if (want_s) s_sum[wv][cell_word<BMAX>(b, lane)] = 0.0f;
     }
 
-    if (d.layout == 1) {
-      const int hb = d.hb[id];  // rows a two-tick pass left empty at the top of the column (tfx_move_tt.hpp)
-      int rows = valid ? n + hb : 0;
-      rows = rows > d.trows ? d.trows : rows;
-      int kmax = rows;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const int q = __shfl_xor(kmax, off, 64);
-        kmax = q > kmax ? q : kmax;
-      }
-      kmax = __builtin_amdgcn_readfirstlane(kmax);
-      const f2v *col = reinterpret_cast<const f2v *>(d.xv + ((size_t)env * G + g) * (size_t)d.trows * 64 + lane);
-      for (int k0 = 0; k0 < kmax; k0 += CELL_P) {
-        f2v c[CELL_P];
-#pragma unroll
-        for (int u = 0; u < CELL_P; ++u) {
-          c[u] = f2v{0.0f, 0.0f};
-          if (k0 + u >= hb && k0 + u < rows) c[u] = col[(size_t)(k0 + u) * 64];
-        }
-#pragma unroll
-        for (int u = 0; u < CELL_P; ++u)
-          if (k0 + u < kmax) w.take(ed, k0 + u >= hb && k0 + u < rows, c[u].x, c[u].y);
-      }
-    } else {
-      int nmax = n;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const int q = __shfl_xor(nmax, off, 64);
-        nmax = q > nmax ? q : nmax;
-      }
-      nmax = __builtin_amdgcn_readfirstlane(nmax);
-      const float2 *row = d.xv + id * C;
-      int slot = ld;
-      for (int k = 0; k < nmax; ++k) {
-        float2 c = make_float2(0.0f, 0.0f);
-        if (k < n) {
-          slot = wrap1(slot + 1, C);
-          c = row[slot];
-        }
-        w.take(ed, k < n, c.x, c.y);
-      }
-    }
+    walk_cars<2, false, true>(d, r, lane, false, [&](bool live, f2v c, float) { w.take(ed, live, c.x, c.y); });
     w.put_back();
 
     // the planes change hands: written per lane, read per (road, cell) pair

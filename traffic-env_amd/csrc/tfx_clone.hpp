@@ -24,7 +24,7 @@
 #pragma once
 #include "tfx_common.hpp"
 #include "tfx_misc.hpp"
-#include "tfx_move_t.hpp"
+#include "tfx_walk.hpp"
 
 namespace tfx {
 
@@ -116,13 +116,7 @@ __global__ __launch_bounds__(256) void k_clone(const Dev dd, const Dev sd, const
       const int hb = sd.hb[sid];
       int rows = valid ? ring_count(ld, lc, C) + hb : 0;  // rows of the column that hold (or lead up to) cars
       rows = rows < 0 ? 0 : (rows > dd.trows ? dd.trows : rows);
-      int kmax = rows;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const int q = __shfl_xor(kmax, off, 64);
-        kmax = q > kmax ? q : kmax;
-      }
-      kmax = __builtin_amdgcn_readfirstlane(kmax);
+      const int kmax = wave_max(rows);
       const size_t scol = ((size_t)s * G + g) * (size_t)sd.trows * 64 + lane;
       const size_t dcol = ((size_t)env * G + g) * (size_t)dd.trows * 64 + lane;
       const f2v *sx = reinterpret_cast<const f2v *>(sd.xv + scol);

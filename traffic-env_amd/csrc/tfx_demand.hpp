@@ -4,7 +4,7 @@
 // The cars of an env in a tick are a pure function of (seed, stream id, clock tick) and two small threshold tables, so
 // the (tick row, env) items share nothing: where k_poisson (tfx_misc.hpp) walks a serial chain per env - a gap decides
 // where the next car falls - this kernel has n_ticks * E independent items.  Decomposition:
-//   * a wavefront per item, four to a workgroup, a stride loop over the items (demand_grid, tfx_launch.hpp);
+//   * a wavefront per item, four to a workgroup, a stride loop over the items (item_grid, tfx_launch.hpp);
 //   * the car count N of the item: one Philox block for the whole wavefront (every lane computes it: no LDS, no
 //     broadcast), lane l compares it with thresholds l, l + 64, ... of the item's count_cdf row (at most four: n_cdf <=
 //     256) and the ballots' population counts add up to N = #{c <= n_cdf - 2 : u0 >= count_cdf[c]};

@@ -1,8 +1,6 @@
 // tfx_frames.hpp - k_frames: top-view RGBA frames of chosen envs (tfx_frames, include/tfx.h) from ONE read of their live
-// cars.  Read-only like k_measure and k_cells, and with their decomposition: a wavefront per (frame, tile) item, four to
-// a workgroup, lane per road through slot_road, a stride loop over the n_frames * G items, the tile's deepest live row
-// reduced across the wavefront, rows walked as coalesced loads with FRAME_P rows in flight, a lane loading only rows
-// hb .. hb + n - 1 of its own column.  Ring layout: each lane walks the ring slots of its road with wrap1.
+// cars.  Read-only like k_measure and k_cells, and on their walk (tfx_walk.hpp) over the n_frames * G (frame, tile)
+// items: x of every car and, in heterogeneous handles, its side word.
 //
 // What is new:
 //   * The env of an item comes from a device array (env_ids[frame]); for an id outside [0, E) nothing of the handle's
@@ -19,12 +17,11 @@
 //     length in the table (a workgroup's LDS copy).
 #pragma once
 #include "tfx_common.hpp"
-#include "tfx_move_t.hpp"
+#include "tfx_walk.hpp"
 
 namespace tfx {
 
-constexpr int FRAME_P = 8;       // rows in flight per wavefront
-constexpr int FRAME_WORDS = 8;   // (TFX_FRAME_PX_MAX - 3 + 31) / 32
+constexpr int FRAME_WORDS = 8;  // (TFX_FRAME_PX_MAX - 3 + 31) / 32
 static_assert(FRAME_WORDS * 32 >= TFX_FRAME_PX_MAX - 3, "a road's pixels fit its bitset");
 // bytes R, G, B, A of a pixel, as the little-endian word a lane stores
 constexpr unsigned PX_GREEN = 0xFF00FF00u, PX_RED = 0xFF0000FFu, PX_YELLOW = 0xFF00FFFFu, PX_CAR = 0xFFFF0000u,
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(256) void k_frames(const Dev d, const FrameArgs f) 
   if (d.het) load_arch(d, s_arch);
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int G = d.G, R = d.R, C = d.C;
+  const int G = d.G;
   const long items = (long)f.n_frames * G;
   const long nw = (long)gridDim.x * 4;
   const int npix = f.S - 3;                 // pixels a road owns: t = 2 .. S - 2
@@ -114,13 +111,9 @@ __global__ __launch_bounds__(256) void k_frames(const Dev d, const FrameArgs f) 
     // what the memset left, or, roads only, its road pixels painted white over whatever an earlier call drew there
     const bool shown = env >= 0 && env < d.E;
     if (!shown && !f.roads_only) continue;
-    const int e_slot = d.slot_road[g * 64 + lane];
-    const bool valid = e_slot >= 0;
-    const bool live = valid && shown;
-    const size_t id = live ? (size_t)env * R + e_slot : 0;
-    const int ld = live ? d.leading[id] : 1;
-    int n = live ? ring_count(ld, d.lastcar[id], C) : 0;
-    n = n < 0 ? 0 : (n > C - 1 ? C - 1 : n);
+    const TileRoad r = tile_road(d, env, g, lane, shown);
+    const int e_slot = r.e_slot;
+    const bool valid = e_slot >= 0, live = r.live;
 
     // the road's light colour (update_colors, traffic_env.py:335-346), start pixel and step
     unsigned colour = shown ? PX_GREEN : PX_WHITE;
@@ -137,44 +130,9 @@ __global__ __launch_bounds__(256) void k_frames(const Dev d, const FrameArgs f) 
 
     for (int w = 0; w < nwords; ++w) bits[w * 64 + lane] = 0u;
 
-    if (d.layout == 1) {
-      const int hb = live ? d.hb[id] : 0;  // rows a two-tick pass left empty at the top of the column (tfx_move_tt.hpp)
-      int rows = n + hb;
-      rows = rows > d.trows ? d.trows : rows;
-      int kmax = rows;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const int q = __shfl_xor(kmax, off, 64);
-        kmax = q > kmax ? q : kmax;
-      }
-      kmax = __builtin_amdgcn_readfirstlane(kmax);
-      const size_t at = ((size_t)(shown ? env : 0) * G + g) * (size_t)d.trows * 64 + lane;
-      const float2 *col = d.xv + at;
-      const float *wcol = d.het ? d.w + at : nullptr;  // the side words travel with the cars
-      for (int k0 = 0; k0 < kmax; k0 += FRAME_P) {
-        float x[FRAME_P], sw[FRAME_P];
-#pragma unroll
-        for (int u = 0; u < FRAME_P; ++u) {
-          x[u] = 0.0f;
-          sw[u] = 0.0f;
-          if (k0 + u >= hb && k0 + u < rows) {
-            x[u] = col[(size_t)(k0 + u) * 64].x;
-            if (d.het) sw[u] = wcol[(size_t)(k0 + u) * 64];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < FRAME_P; ++u)
-          if (k0 + u >= hb && k0 + u < rows)
-            frame_mark(bits, lane, x[u], d.het ? s_arch[side_arch(sw[u]) * ARCH_W + AR_L] : d.car_l, f.k, top);
-      }
-    } else {
-      const float2 *row = d.xv + id * C;
-      int slot = ld;
-      for (int k = 0; k < n; ++k) {
-        slot = wrap1(slot + 1, C);
-        frame_mark(bits, lane, row[slot].x, d.het ? s_arch[side_arch(d.w[id * C + slot]) * ARCH_W + AR_L] : d.car_l, f.k, top);
-      }
-    }
+    walk_cars<1, true, false>(d, r, lane, d.het, [&](bool, f2v c, float sw) {
+      frame_mark(bits, lane, c.x, d.het ? s_arch[side_arch(sw) * ARCH_W + AR_L] : d.car_l, f.k, top);
+    });
 
     // the bitset changes hands: written per lane, read per (road, pixel) pair
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -1123,19 +1123,12 @@ int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_me
   o.queue = out->queue;
   o.speed_sum = out->speed_sum;
   o.accumulate = (flags & TFX_MEASURE_ACCUMULATE) ? 1 : 0;
-  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
-  hipLaunchKernelGGL(k_measure, dim3((unsigned)tile_grid(h, true)), dim3(256), 0, (hipStream_t)stream, h->d, halt_speed,
-                     x_from, o);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+  return launch_query(k_measure, tile_grid(h, true), stream, h->d, halt_speed, x_from, o);
 }
 
 int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
-  const long g = tile_grid(h, true);
-  if (grid) *grid = (int32_t)g;
-  if (waves) *waves = (int32_t)(g * 4);
-  return TFX_OK;
+  return report_launch(tile_grid(h, true), grid, waves);
 }
 
 int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *stream) {
@@ -1150,18 +1143,12 @@ int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *
   o.age_sum = reinterpret_cast<long long *>(out->age_sum);
   o.age_max = out->age_max;
   o.accumulate = (flags & TFX_TRAVEL_ACCUMULATE) ? 1 : 0;
-  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
-  hipLaunchKernelGGL(k_ages, dim3((unsigned)tile_grid(h, true)), dim3(256), 0, (hipStream_t)stream, h->d, o);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+  return launch_query(k_ages, tile_grid(h, true), stream, h->d, o);
 }
 
 int tfx_ages_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
-  const long g = tile_grid(h, true);
-  if (grid) *grid = (int32_t)g;
-  if (waves) *waves = (int32_t)(g * 4);
-  return TFX_OK;
+  return report_launch(tile_grid(h, true), grid, waves);
 }
 
 int tfx_trip_stats(tfx_handle h, const int32_t *edges, int32_t n_bins, int32_t *cursor, const tfx_trip_stat_buffers *out,
@@ -1192,11 +1179,8 @@ int tfx_trip_stats(tfx_handle h, const int32_t *edges, int32_t n_bins, int32_t *
   o.lost = out->lost;
   o.hist = out->hist;
   o.accumulate = (flags & TFX_TRAVEL_ACCUMULATE) ? 1 : 0;
-  // Not counted by tfx_debug_fail_after; only the caller's cursor and outputs are written: captured graphs stay valid.
-  hipLaunchKernelGGL(k_trips, dim3((unsigned)trips_grid(h)), dim3(256), 0, (hipStream_t)stream, h->d, ed,
-                     out->hist ? n_bins : 0, cursor, o);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+  // a wavefront per env; of the caller's memory the cursor is written next to the outputs
+  return launch_query(k_trips, item_grid(h, h->d.E), stream, h->d, ed, out->hist ? n_bins : 0, cursor, o);
 }
 
 int tfx_road_cells(tfx_handle h, const float *edges, int32_t n_cells, const tfx_cell_buffers *out, int32_t flags,
@@ -1222,28 +1206,16 @@ int tfx_road_cells(tfx_handle h, const float *edges, int32_t n_cells, const tfx_
   o.n_cars = out->n_cars;
   o.speed_sum = out->speed_sum;
   o.accumulate = (flags & TFX_CELLS_ACCUMULATE) ? 1 : 0;
-  // k_measure's launch (tile_grid), instantiated on the cell bound.
-  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
-  const dim3 grid((unsigned)tile_grid(h, true));
+  // k_measure's launch (tile_grid), instantiated on the cell bound
   const int B = n_cells;
-  if (B <= 8)
-    hipLaunchKernelGGL(k_cells<8>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
-  else if (B <= 16)
-    hipLaunchKernelGGL(k_cells<16>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
-  else
-    hipLaunchKernelGGL(k_cells<32>, grid, dim3(256), 0, (hipStream_t)stream, h->d, ed, B, o);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+  return launch_query(B <= 8 ? k_cells<8> : B <= 16 ? k_cells<16> : k_cells<32>, tile_grid(h, true), stream, h->d, ed, B, o);
 }
 
 int tfx_cells_launch(tfx_handle h, int32_t n_cells, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
   if (n_cells < 1 || n_cells > TFX_MAX_CELLS)
     return fail(TFX_EINVAL, "cells: n_cells %d is outside 1..%d", n_cells, TFX_MAX_CELLS);
-  const long g = tile_grid(h, true);
-  if (grid) *grid = (int32_t)g;
-  if (waves) *waves = (int32_t)(g * 4);
-  return TFX_OK;
+  return report_launch(tile_grid(h, true), grid, waves);
 }
 
 // the px of the three frame calls
@@ -1285,22 +1257,16 @@ int tfx_frames(tfx_handle h, const int32_t *env_ids, int32_t n_frames, int32_t p
   f.W = (int)W;
   f.H = (int)H;
   f.k = (float)(px - 3) / h->cfg.length;  // one float32 division, on the host
-  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
   if (!(flags & TFX_FRAMES_ROADS_ONLY))
     HIPCHK(hipMemsetAsync(out, 0xFF, (size_t)n_frames * (size_t)(W * H) * 4, (hipStream_t)stream));
-  hipLaunchKernelGGL(k_frames, dim3((unsigned)tile_grid(h, true, n_frames)), dim3(256), 0, (hipStream_t)stream, h->d, f);
-  HIPCHK(hipGetLastError());
-  return TFX_OK;
+  return launch_query(k_frames, tile_grid(h, true, n_frames), stream, h->d, f);
 }
 
 int tfx_frames_launch(tfx_handle h, int32_t n_frames, int32_t px, int32_t *grid, int32_t *waves) {
   if (n_frames < 1) return fail(TFX_EINVAL, "frames: n_frames %d is less than 1", n_frames);
   if (int rc = frame_px_ok(px)) return rc;
   if (int rc = check_handle(h, false)) return rc;
-  const long g = tile_grid(h, true, n_frames);
-  if (grid) *grid = (int32_t)g;
-  if (waves) *waves = (int32_t)(g * 4);
-  return TFX_OK;
+  return report_launch(tile_grid(h, true, n_frames), grid, waves);
 }
 
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream) {

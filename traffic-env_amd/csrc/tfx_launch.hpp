@@ -144,17 +144,39 @@ int grid_for(const tfx_handle_s *h, long items) {
   return (int)grid_capped(h, g);
 }
 
-// Grid of the kernels that take a wavefront per (env, tile), four to a workgroup (k_clone, k_measure, k_cells): a few
-// workgroups per compute unit stride over more; TFX_MEASURE_GRID caps the measures' and the cells' launches instead
-// (tests of their stride loops; TFX_GRID_CAP caps the others, and these too where TFX_MEASURE_GRID is not set).
-// n_frames > 0: k_frames' launch, capped like the cells' - its items are (frame, tile) pairs of the frames drawn
-long tile_grid(const tfx_handle_s *h, bool measure = false, long n_frames = 0) {
-  long grid = ((n_frames > 0 ? n_frames : (long)h->d.E) * h->d.G + 3) / 4;
+// Grid of the kernels that take a wavefront per item, four to a workgroup: at most 16 workgroups per compute unit
+// stride over more.  (k_demand: (tick row, env) items; k_trips: envs; the rest: tile_grid.)
+// measure: TFX_MEASURE_GRID, where set, caps the launch instead (tests of the stride loops; TFX_GRID_CAP caps the
+// others, and these too where TFX_MEASURE_GRID is not set)
+long item_grid(const tfx_handle_s *h, long items, bool measure = false) {
+  long grid = (items + 3) / 4;
   const bool own = measure && h->measure_grid > 0;
   const long cap = own ? (long)h->measure_grid : (long)h->n_cu * 16;
   if (grid > cap) grid = cap;
   if (grid < 1) grid = 1;
   return own ? grid : grid_capped(h, grid);
+}
+
+// ... of the kernels whose items are (env, tile) pairs: k_clone, and in the measure form k_measure, k_ages and k_cells.
+// n_frames > 0: k_frames' launch - its items are (frame, tile) pairs of the frames drawn
+long tile_grid(const tfx_handle_s *h, bool measure = false, long n_frames = 0) {
+  return item_grid(h, (n_frames > 0 ? n_frames : (long)h->d.E) * h->d.G, measure);
+}
+
+// A query kernel - 256 lanes, no dynamic LDS - on the caller's stream.  Not counted by tfx_debug_fail_after, and
+// nothing in the handle changes: captured graphs stay valid.
+template <class... Params, class... Args>
+int launch_query(void (*kern)(Params...), long grid, void *stream, Args... args) {
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, args...);
+  HIPCHK(hipGetLastError());
+  return TFX_OK;
+}
+
+// What the tfx_*_launch entries report of a grid of `grid` workgroups (test support)
+int report_launch(long grid, int32_t *grid_out, int32_t *waves_out) {
+  if (grid_out) *grid_out = (int32_t)grid;
+  if (waves_out) *waves_out = (int32_t)(grid * 4);
+  return TFX_OK;
 }
 
 // The on-device Poisson stream for the next n_ticks ticks (rows of the count buffer); one workgroup per env, as
@@ -174,32 +196,12 @@ int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
   return TFX_OK;
 }
 
-// Grid of k_demand (tfx_demand.hpp): a wavefront per (tick row, env) item, four to a workgroup; a few workgroups per
-// compute unit stride over more, as tile_grid's kernels do
-long demand_grid(const tfx_handle_s *h, int n_ticks) {
-  long grid = ((long)n_ticks * h->d.E + 3) / 4;
-  const long cap = (long)h->n_cu * 16;
-  if (grid > cap) grid = cap;
-  if (grid < 1) grid = 1;
-  return grid_capped(h, grid);
-}
-
-// Grid of k_trips (tfx_travel.hpp): a wavefront per env, four to a workgroup; a few workgroups per compute unit stride
-// over more.  (k_ages takes tile_grid's measure form, like k_measure.)
-long trips_grid(const tfx_handle_s *h) {
-  long grid = ((long)h->d.E + 3) / 4;
-  const long cap = (long)h->n_cu * 16;
-  if (grid > cap) grid = cap;
-  if (grid < 1) grid = 1;
-  return grid_capped(h, grid);
-}
-
 // Rule 4's rows for n_ticks clock ticks into `out` - from the device clock on (use_clock: the rows of a call about to
 // be enqueued on st) or from tick0 on (the preview).  One launch; it writes nothing but `out`.
 int launch_demand(tfx_handle h, int use_clock, int tick0, int n_ticks, int *out, hipStream_t st) {
   const size_t lds = (size_t)4 * 2 * h->d.n_entry * sizeof(unsigned);
-  hipLaunchKernelGGL(k_demand, dim3((unsigned)demand_grid(h, n_ticks)), dim3(256), lds, st, h->d, h->stream.dm, use_clock,
-                     tick0, n_ticks, out);
+  const long grid = item_grid(h, (long)n_ticks * h->d.E);  // a wavefront per (tick row, env)
+  hipLaunchKernelGGL(k_demand, dim3((unsigned)grid), dim3(256), lds, st, h->d, h->stream.dm, use_clock, tick0, n_ticks, out);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }

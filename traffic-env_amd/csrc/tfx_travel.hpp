@@ -1,17 +1,10 @@
 // tfx_travel.hpp - travel times on the device (tfx_car_ages, tfx_trip_stats, include/tfx.h): two read-only kernels.
 //
 // k_ages: how long every live car has been on the map, per road - the count, the int64 sum and the maximum of
-// side_age(now, side word), `now` read from the handle's device clock as k_clone reads it.  It is k_measure's walk
-// (tfx_measure.hpp) over the SIDE plane only: one wavefront per (env, tile), lane per road;
-//   * the lane of storage slot 64 * tile + j loads its road's leading / lastcar / hb; the wavefront reduces the tile's
-//     deepest live row;
-//   * rows 0 .. kmax-1 of the tile's side plane are walked as 64 x 4 B row loads (256 B per row and wavefront),
-//     coalesced, MEAS_P rows in flight; a lane loads the rows its own road has cars in (hb <= k < n + hb) and no others;
-//     xv is never read;
-//   * three running integers per lane, stored (or, TFX_TRAVEL_ACCUMULATE, added / maxed) at [env][road id].
+// side_age(now, side word), `now` read from the handle's device clock as k_clone reads it.  The shared walk of the road
+// kernels (tfx_walk.hpp) over the SIDE plane only - 64 x 4 B row loads; xv is never read - with three running integers
+// per lane, stored (or, TFX_TRAVEL_ACCUMULATE, added / maxed) at [env][road id].
 // Integer arithmetic throughout: the order of the cars does not matter, both layouts and a host loop give the same bits.
-// Ring layout: each lane walks the ring slots of its road from leading + 1 with wrap1.
-// (A kernel of its own rather than a second accumulator type over k_measure's walk: k_measure's code stays what it was.)
 //
 // k_trips: the finished trips, reduced where advance_hack's device forms log them (trip_times / n_trips of the bound
 // buffers).  One wavefront per env, four to a workgroup, striding over the envs; the lanes stride the span
@@ -25,7 +18,7 @@
 // (TrafficVecEnv.travel_times does).
 #pragma once
 #include "tfx_common.hpp"
-#include "tfx_measure.hpp"
+#include "tfx_walk.hpp"
 
 namespace tfx {
 
@@ -40,60 +33,25 @@ struct AgeOut {
 __global__ __launch_bounds__(256) void k_ages(const Dev d, const AgeOut o) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int G = d.G, R = d.R, C = d.C;
+  const int G = d.G;
   const long items = (long)d.E * G;
   const long nw = (long)gridDim.x * 4;
   const int now = *d.tickA;
 
   for (long item = (long)blockIdx.x * 4 + wv; item < items; item += nw) {
     const int env = (int)(item / G);
-    const int g = (int)(item - (long)env * G);
-    const int e_slot = d.slot_road[g * 64 + lane];
-    const bool valid = e_slot >= 0;
-    const size_t id = (size_t)env * R + (valid ? e_slot : 0);
-    const int ld = d.leading[id];
-    int n = valid ? ring_count(ld, d.lastcar[id], C) : 0;
-    n = n < 0 ? 0 : (n > C - 1 ? C - 1 : n);
+    const TileRoad r = tile_road(d, env, (int)(item - (long)env * G), lane);
+    const size_t id = r.id;
+    const int n = r.n;
     int amax = 0;
     long long asum = 0;
+    walk_cars<0, true, false>(d, r, lane, true, [&](bool, f2v, float sw) {
+      const int a = (int)side_age(d, now, sw);
+      asum += a;
+      amax = a > amax ? a : amax;
+    });
 
-    if (d.layout == 1) {
-      const int hb = d.hb[id];  // rows a two-tick pass left empty at the top of the column (tfx_move_tt.hpp)
-      int rows = valid ? n + hb : 0;
-      rows = rows > d.trows ? d.trows : rows;
-      int kmax = rows;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const int q = __shfl_xor(kmax, off, 64);
-        kmax = q > kmax ? q : kmax;
-      }
-      kmax = __builtin_amdgcn_readfirstlane(kmax);
-      const float *col = d.w + ((size_t)env * G + g) * (size_t)d.trows * 64 + lane;
-      for (int k0 = 0; k0 < kmax; k0 += MEAS_P) {
-        float c[MEAS_P];
-#pragma unroll
-        for (int u = 0; u < MEAS_P; ++u)
-          if (k0 + u >= hb && k0 + u < rows) c[u] = col[(size_t)(k0 + u) * 64];
-#pragma unroll
-        for (int u = 0; u < MEAS_P; ++u)
-          if (k0 + u >= hb && k0 + u < rows) {
-            const int a = (int)side_age(d, now, c[u]);
-            asum += a;
-            amax = a > amax ? a : amax;
-          }
-      }
-    } else {
-      const float *row = d.w + id * C;
-      int slot = ld;
-      for (int k = 0; k < n; ++k) {
-        slot = wrap1(slot + 1, C);
-        const int a = (int)side_age(d, now, row[slot]);
-        asum += a;
-        amax = a > amax ? a : amax;
-      }
-    }
-
-    if (valid) {
+    if (r.live) {
       if (o.accumulate) {
         if (o.n_cars) o.n_cars[id] += n;
         if (o.age_sum) o.age_sum[id] += asum;
