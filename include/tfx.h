@@ -175,7 +175,8 @@ int tfx_set_spawns(tfx_handle h, int32_t mode, const int32_t *dev, int32_t perio
  * g in a tick, and let s be the number of cars the stream has put on that entry road of that env before this tick
  * (every car made counts, overflowed ones included; an env that stands still in an agent step makes none).  Its row is
  *     row = (u0 * n_archetypes) >> 32,  u = philox4x32(ctr = {s + j, g, TAG_ARCH, ej}, key = seed)
- * with TAG_ARCH = 0x41524348 (the gap and road draws use 0x47415021 / 0x524F4144 and keep their indices: the counts
+ * with TAG_ARCH = 0x41524348 (the gap and road draws use 0x47415021 / 0x524F4144 and keep their indices; rules 2 - 5 use
+ * 0x45504953, 0x504F4F4C, 0x44434E54 / 0x44524F44 and 0x44524F57: the counts
  * are those of a single-archetype handle with the same seed).  Rows are stored for j < S = C - 2 only: no road takes
  * more cars in one tick (add_car, traffic_env.py:97-114; the cars past it overflow), so no car past it reaches a road.
  * The stream's rows stay bound until a later tfx_set_spawns (which unbinds them: cars get row 0 unless a
@@ -223,7 +224,7 @@ int tfx_set_spawn_archetypes(tfx_handle h, const uint8_t *dev, int32_t per_road,
  *                          ej = #{j in 0 .. n_entry-2 : w >= road_cdf[k][s][j]}
  *     counts[env][ej] += 1
  * with TAG_DCNT = 0x44434E54 and TAG_DROAD = 0x44524F44 (the other draws use 0x47415021, 0x524F4144, 0x41524348,
- * 0x45504953 and 0x504F4F4C).  Comparisons and integer adds only: the device (k_demand, csrc/tfx_demand.hpp), the host
+ * 0x45504953, 0x504F4F4C and, rule 5, 0x44524F57).  Comparisons and integer adds only: the device (k_demand, csrc/tfx_demand.hpp), the host
  * mirror (devrng.demand_counts) and any sharding of the envs over handles agree to the bit.  Cars beyond what a road
  * takes in a tick overflow, as with any count buffer.  The rule reads the handle's clock, like TFX_ACTION_CYCLE and
  * TFX_SPAWN_PERIODIC: it is an input of the handle, nothing about it is reset by tfx_reset, tfx_reset_envs or an episode
@@ -237,8 +238,8 @@ int tfx_set_spawn_archetypes(tfx_handle h, const uint8_t *dev, int32_t per_road,
  * tfx_set_demand replaces any earlier spawn rule, as tfx_set_poisson does; a later tfx_set_spawns / tfx_set_poisson /
  * tfx_set_regular replaces it.  TFX_EINVAL, naming the field: a null struct or null tables, sizes out of range, a
  * period that does not fit an int32, a table row that is not non-decreasing or does not end in 0xFFFFFFFF, no entry
- * roads or more than 2048, a heterogeneous handle (archetype rows for this rule are not drawn yet).  TFX_ESTATE before
- * tfx_bind_buffers.  A refused call changes nothing.
+ * roads or more than 2048, a heterogeneous handle (rule 4 draws no archetype rows: tfx_set_demand_mixed, below, draws
+ * them).  TFX_ESTATE before tfx_bind_buffers.  A refused call changes nothing.
  *
  * tfx_clone_envs with TFX_CLONE_STREAM between two demand handles copies the stream id, so source and clone receive the
  * same cars from then on (under the same profile_of_env entries, which are the caller's); it needs an equal seed, sizes,
@@ -256,6 +257,44 @@ int tfx_set_demand(tfx_handle h, const tfx_demand *dm);
  * tfx_debug_fail_after does not count the launch.  TFX_EINVAL: a NULL handle, NULL `out`, a negative n_ticks;
  * TFX_ESTATE before tfx_bind_buffers or without a demand. */
 int tfx_demand_counts(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *out, void *stream);
+
+/* Demand profiles for heterogeneous handles (tfx_config.n_archetypes): rule 4's cars, each with an archetype-table row
+ * drawn by (profile, segment) weights - a truck share that follows the time of day and differs from env to env.
+ * row_cdf is a third HOST table (copied by the call; devrng.demand_row_table builds it) in the format of road_cdf:
+ *   row_cdf[K][S][n_rows], n_rows = the handle's n_archetypes: the cumulative weights of the rows scaled by 2^32, every
+ *   row of the table non-decreasing, its last entry 0xFFFFFFFF.  A row of weight zero is not drawn.
+ *
+ * Rule 5.  Take car c (0 <= c < N) of rule 4's item (clock tick t, stream id g, profile k, segment s), and let ej be the
+ * entry road rule 4 gives it:
+ *     v   = word (c & 3) of philox4x32(ctr = {t, g, TAG_DROW, c >> 2}, key = seed)
+ *     row = #{i in 0 .. n_rows-2 : v >= row_cdf[k][s][i]}
+ *     j   = #{c' < c : ej(c') == ej}           (creation order on a road = car-index order)
+ *     rows[tick][env][ej][j] = row             if j < S,   S = min(C - 2, n_cdf - 1)
+ * with TAG_DROW = 0x44524F57.  Comparisons and integer adds only; the counts are exactly rule 4's, and the new draws use
+ * a tag of their own: a single-archetype handle with the same seed sees the same cars.  S loses nothing: no road takes
+ * more than C - 2 cars in a tick (the cars past it overflow) and no env receives more than n_cdf - 1.  Entries of a road
+ * past min(count, S) are unspecified (nobody reads them; the mirror, devrng.demand_rows, returns 0 there).  Like rule 4
+ * the rule is stateless: restarts, warm pools, clones and clocks need nothing new, and an env that stops in a decision
+ * does not consume the later rows.
+ *
+ * The call makes every check tfx_set_demand makes, and returns TFX_EINVAL, naming the field, for a null row_cdf, n_rows
+ * other than the handle's n_archetypes, a row_cdf row that decreases or does not end in 0xFFFFFFFF, and a handle that is
+ * not heterogeneous (that one takes tfx_set_demand); TFX_ESTATE before tfx_bind_buffers.  A refused call changes nothing.
+ * It replaces any earlier spawn rule and binds the rows it draws as the spawn rows, per tick like the counts, wherever
+ * the cars move (tfx_step, tfx_agent_step, tfx_move_cars); a later tfx_set_spawns, tfx_set_poisson, tfx_set_regular,
+ * tfx_set_demand or tfx_set_spawn_archetypes does what it does after a tfx_set_poisson stream's rows.  A decision must
+ * fit the rows the handle's buffer holds: counts and archetype rows share one chunk (64 ticks, fewer beyond 32 MB of
+ * counts or 256 MB of rows: 16 at 4096 envs x 64 entry roads x S = 64).  tfx_demand_counts works as on a plain demand.
+ * tfx_clone_envs with TFX_CLONE_STREAM compares row_cdf with the other tables ("demand tables"). */
+int tfx_set_demand_mixed(tfx_handle h, const tfx_demand *dm, const uint32_t *row_cdf, int32_t n_rows);
+/* Rules 4 and 5 together for clock ticks tick0 .. tick0 + n_ticks - 1, into the caller's device buffers: counts int32
+ * [n_ticks][E][n_entry] (what tfx_demand_counts gives) and rows uint8 [n_ticks][E][n_entry][S] (entry j of a road is
+ * written for j < min(count, S), the rest is left as it was).  Read-only, one launch on `stream`, no host
+ * synchronisation; captured graphs stay valid and tfx_debug_fail_after does not count the launch.  TFX_EINVAL: a NULL
+ * handle or buffer, a negative n_ticks; TFX_ESTATE before tfx_bind_buffers or without a mixed demand. */
+int tfx_demand_rows(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *counts, uint8_t *rows, void *stream);
+/* S of rule 5 for the mixed demand the handle holds.  TFX_ESTATE without one. */
+int tfx_demand_rows_per_road(tfx_handle h, int32_t *per_road);
 
 /* TrafficEnv._step (traffic_env.py:224-248), n_ticks times: phase/elapsed update, spawns,
  * move_cars, advance_finished_cars | advance_hack, steps += 1. */

@@ -4,9 +4,12 @@ the E-W ones do - at two demand levels spread over the envs of the batch (profil
 times as much).  The fixed cycle and the on-device greedy controller (TFX_ACTION_GREEDY, algorithms/greedy.py:14-16) run
 on the same seed, so on the same cars; an asymmetric demand is where the two differ at all.  Prints both mean returns per
 env and, from the read-only preview tfx_demand_counts, the cars every segment brought and the share of them that
-entered on N-S roads.
+entered on N-S roads.  --trucks SHARE_PEAK,SHARE_OFF makes the cars of two kinds (tfx_set_demand_mixed, rule 5): a table of
+two archetype rows, car and truck, the trucks' share of the arrivals by segment (segment 0 is the peak); a `rows` line
+then gives the share of trucks among the cars every segment spawned, from the preview tfx_demand_rows.
 
     python tools/demand_demo.py --envs 256 --decisions 120
+    python tools/demand_demo.py --envs 256 --decisions 120 --trucks 0.4,0.1
 """
 import argparse
 import os
@@ -33,9 +36,17 @@ def tidal(a):
     return means, np.stack([w, w]), ns
 
 
+# rows (v, l, a, delta, v0, b, T, s0) of the archetype table under --trucks: the reference's car, and a long slow truck
+CAR_AND_TRUCK = [[11.11, 4.0, 3.0, 4.0, 13.89, 6.0, 2.0, 1.0], [8.0, 8.0, 1.5, 4.0, 10.0, 4.0, 2.5, 2.0]]
+
+
 def make(a, means, weights):
-    venv = TrafficVecEnv(a.envs, a.m, a.n, a.length, capacity=a.capacity, spawn='demand', seed=a.seed,
-                         demand=dict(means=means, weights=weights, seg_ticks=a.seg_decisions * a.ticks, tick_offset=0))
+    mixed = {}
+    demand = dict(means=means, weights=weights, seg_ticks=a.seg_decisions * a.ticks, tick_offset=0)
+    if a.trucks is not None:
+        mixed = dict(archetypes=CAR_AND_TRUCK)
+        demand["row_weights"] = [[[1.0 - share, share] for share in a.trucks]] * 2      # [profile][segment][car, truck]
+    venv = TrafficVecEnv(a.envs, a.m, a.n, a.length, capacity=a.capacity, spawn='demand', seed=a.seed, demand=demand, **mixed)
     venv.demand_profile.copy_(torch.arange(a.envs, device=venv.engine.device, dtype=torch.int32) % 2)    # two levels
     return venv
 
@@ -60,12 +71,18 @@ def run(a):
     seg_ticks = a.seg_decisions * T
     north_south = torch.as_tensor(ns > 0, device=eng.device)
     per_seg = np.zeros((2, 2), np.int64)                            # [segment][all cars, N-S cars]
+    trucks = np.zeros((2, 2), np.int64)                             # [segment][cars with a row, trucks among them]
     for t0 in range(0, a.decisions * T, seg_ticks):
         n = min(seg_ticks, a.decisions * T - t0)
-        c = eng.demand_counts(t0, n).sum(dim=(0, 1))
         s = (t0 // seg_ticks) % 2
+        if a.trucks is None:
+            c = eng.demand_counts(t0, n).sum(dim=(0, 1))
+        else:
+            c, rows = eng.demand_rows(t0, n)            # (row 1 is the truck; the entries past a road's cars are 0)
+            trucks[s] += [int(c.clamp(max=rows.shape[-1]).sum()), int(rows.sum())]
+            c = c.sum(dim=(0, 1))
         per_seg[s] += [int(c.sum()), int(c[north_south].sum())]
-    return rets, per_seg
+    return rets, per_seg, trucks
 
 
 def main(argv=None):
@@ -83,9 +100,15 @@ def main(argv=None):
     ap.add_argument("--boost", type=float, default=1.5, help="demand level of profile 1 relative to profile 0")
     ap.add_argument("--cycle", type=int, default=20, help="ticks per phase of the fixed cycle")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--trucks", default=None, metavar="SHARE_PEAK,SHARE_OFF",
+                    help="two kinds of cars: the trucks' share of the arrivals in segment 0 and in segment 1")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
-    rets, per_seg = run(a)
+    if a.trucks is not None:
+        a.trucks = [float(x) for x in a.trucks.split(",")]
+        if len(a.trucks) != 2 or not all(0.0 <= x <= 1.0 for x in a.trucks):
+            ap.error("--trucks takes two shares in [0, 1]: SHARE_PEAK,SHARE_OFF")
+    rets, per_seg, trucks = run(a)
     lines = ["demand demo: %d envs (%dx%d grid, L=%g, C=%d), %d decisions of %d ticks, segments of %d decisions, tide x%g, "
              "every second env at x%g" % (a.envs, a.m, a.n, a.length, a.capacity, a.decisions, a.ticks, a.seg_decisions,
                                           a.tide, a.boost),
@@ -94,6 +117,9 @@ def main(argv=None):
     for s, label in enumerate(("N-S heavy", "E-W heavy")):
         cars, ns = per_seg[s]
         lines.append("segment %d (%s): cars %d over the batch, N-S share %.3f" % (s, label, cars, ns / max(1, cars)))
+    if a.trucks is not None:
+        lines.append("rows: trucks among the cars spawned, " + ", ".join(
+            "segment %d: %.3f (asked %.3f)" % (s, trucks[s][1] / max(1, trucks[s][0]), a.trucks[s]) for s in range(2)))
     for ln in lines:
         print(ln)
     if a.out:

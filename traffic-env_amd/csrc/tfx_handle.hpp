@@ -68,13 +68,18 @@ struct ArrivalStream {
   unsigned *draws = nullptr, *sid = nullptr;
   unsigned *tables = nullptr;
   // rule 1: k_poisson's and k_res's arguments, the archetype rows of heterogeneous cars (rows == nullptr: none drawn;
-  // bound as Dev::spawn_arch while d.spawn_arch == prow.rows), the rate the Poisson stream was set up with
+  // bound as Dev::spawn_arch while d.spawn_arch == prow.rows), the rate the Poisson stream was set up with.  A mixed
+  // demand (rule 5) keeps its rows region in prow.rows / prow.S as well: one place says what the stream bound
   PoissonDev ps{};
   PoissonRows prow{};
   double rate = 0.0;
   // rule 4: k_demand's arguments, the host copies of its tables (two handles must hold the same to share a stream)
   DemandDev dm{};
   std::vector<uint32_t> count_cdf, road_cdf;
+  // rule 5 (tfx_set_demand_mixed): k_demand<true>'s further arguments and the host copy of the third table
+  DemandRows drow{};
+  std::vector<uint32_t> row_cdf;
+  bool mixed() const { return kind == STREAM_DEMAND && drow.row_cdf != nullptr; }
   bool drawn() const { return kind != STREAM_NONE; }
   // rule 4 is stateless: every caller draws the rows of its ticks up front, from the device clock on
   bool upfront() const { return kind == STREAM_DEMAND; }
@@ -150,7 +155,7 @@ struct tfx_handle_s {
   unsigned long long input_gen = 0;
   bool use_graph = true;  // TFX_GRAPH=0 disables
   int fail_after = 0;  // tfx_debug_fail_after: the n-th launch from now fails (error-path tests); 0 = off
-  // the arrival stream drawn on the device, if any (tfx_set_poisson / tfx_set_regular / tfx_set_demand)
+  // the arrival stream drawn on the device, if any (tfx_set_poisson / tfx_set_regular / tfx_set_demand / tfx_set_demand_mixed)
   ArrivalStream stream;
   // greedy controller (own buffer)
   bool greedy = false;

@@ -45,7 +45,7 @@ void stream_key(const ArrivalStream &a, std::string &key) {
   const PoissonDev &p = a.ps;
   const DemandDev &m = a.dm;
   key_put(key, a.kind, p.seed_lo, p.seed_hi, p.n_cdf, p.regular, p.every, p.burst, m.K, m.S, m.seg_ticks, m.tick_offset, m.n_cdf,
-          m.seed_lo, m.seed_hi, m.profile, a.buf);
+          m.seed_lo, m.seed_hi, m.profile, a.drow.n_rows, a.drow.S, a.buf);
 }
 
 // Everything a captured launch sequence bakes into its kernel arguments (a stale graph is never replayed, even when a
@@ -165,14 +165,16 @@ void drop_stream(tfx_handle h) {
 // gap at -1: first gap not drawn yet -, every env's stream keyed by its global id (tfx_clone_envs with
 // TFX_CLONE_STREAM copies ids), the kind's tables uploaded one behind the other.  The setter adds the kind's scalars.
 struct HostTable { const uint32_t *words; size_t n; };
-int stage_stream(tfx_handle h, StreamKind kind, uint64_t seed, std::initializer_list<HostTable> tables, ArrivalStream *out) {
+int stage_stream(tfx_handle h, StreamKind kind, uint64_t seed, std::initializer_list<HostTable> tables, ArrivalStream *out,
+                 int demand_rows = 0) {
   const Dev &d = h->d;
   const bool demand = kind == STREAM_DEMAND;
   size_t n_tables = 0;
   for (const HostTable &t : tables) n_tables += t.n;
-  // heterogeneous cars: the Poisson stream draws every car's archetype row (the regular stream's cars are row 0)
-  const int S = kind == STREAM_POISSON && h->het ? d.C - 2 : 0;
-  const StreamLayout l = stream_layout(d.E, d.n_entry, n_tables, S);
+  // heterogeneous cars: the Poisson stream draws every car's archetype row (the regular stream's cars are row 0), a mixed
+  // demand demand_rows of them per road and tick - with no car counters to keep (rule 5 is stateless)
+  const int S = kind == STREAM_POISSON && h->het ? d.C - 2 : (demand ? demand_rows : 0);
+  const StreamLayout l = stream_layout(d.E, d.n_entry, n_tables, S, demand);
   ArrivalStream s;
   if (hipMalloc(&s.buf, l.bytes) != hipSuccess) {
     const hipError_t e = hipGetLastError();
@@ -194,7 +196,7 @@ int stage_stream(tfx_handle h, StreamKind kind, uint64_t seed, std::initializer_
             hipMemcpy(s.sid, ids.data(), ids.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
   unsigned *to = s.tables;
   for (const HostTable &t : tables) {
-    ok = ok && hipMemcpy(to, t.words, t.n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && (t.n == 0 || hipMemcpy(to, t.words, t.n * 4, hipMemcpyHostToDevice) == hipSuccess);
     to += t.n;
   }
   if (!ok) {
@@ -216,7 +218,7 @@ int stage_stream(tfx_handle h, StreamKind kind, uint64_t seed, std::initializer_
     s.ps.seed_hi = (unsigned)(seed >> 32);
   }
   if (S > 0) {
-    s.prow.seq = (unsigned *)(base + l.seq);
+    s.prow.seq = demand ? nullptr : (unsigned *)(base + l.seq);
     s.prow.rows = (uint8_t *)(base + l.arch);
     s.prow.S = S;
     s.prow.n_arch = h->n_arch;
@@ -228,7 +230,8 @@ int stage_stream(tfx_handle h, StreamKind kind, uint64_t seed, std::initializer_
 // The staged stream replaces whatever spawn rule the handle had.  What the move kernels see: a count buffer of the
 // handle's own - per tick for rule 4, whose callers draw their rows up front; one row for rule 1 (tfx_step's chunks set
 // the strides of theirs, for_stream_chunks) - and the stream's archetype rows or, where it draws none (every car of the
-// regular stream is archetypes[0], traffic_env.py:174), no rows at all.
+// regular stream is archetypes[0], traffic_env.py:174), no rows at all.  The rows of a mixed demand are per tick like
+// its counts: the stride holds wherever the move kernels run - decisions and tfx_move_cars as well as tfx_step's chunks.
 void install_stream(tfx_handle h, ArrivalStream &&s) {
   Dev &d = h->d;
   ++h->input_gen;
@@ -241,7 +244,78 @@ void install_stream(tfx_handle h, ArrivalStream &&s) {
   h->spawn_per_tick = a.upfront() ? 1 : 0;
   d.spawn_arch = a.prow.rows;
   d.spawn_arch_S = a.prow.S;
-  d.spawn_arch_stride = 0;
+  d.spawn_arch_stride = a.upfront() ? d.spawn_stride * a.prow.S : 0;
+}
+
+// a threshold table's row: non-decreasing, the last one 0xFFFFFFFF (k_demand's binary search relies on the order).
+// 0: fine; c < n: the row decreases at c; n: it does not end in 0xFFFFFFFF
+int bad_cdf_row(const uint32_t *row, int n) {
+  for (int c = 1; c < n; ++c)
+    if (row[c] < row[c - 1]) return c;
+  return row[n - 1] != 0xFFFFFFFFu ? n : 0;
+}
+
+// tfx_set_demand (mixed false: rule 4 alone) and tfx_set_demand_mixed (rule 5 as well: row_cdf [K][S][n_rows]).
+// (the arguments first, as tfx_road_cells checks them: each cause is named whatever state the handle is in)
+int set_demand(tfx_handle h, const tfx_demand *dm, bool mixed, const uint32_t *row_cdf, int32_t n_rows) {
+  if (!dm) return fail(TFX_EINVAL, "demand: dm is null");
+  if (!dm->count_cdf) return fail(TFX_EINVAL, "demand: count_cdf is null");
+  if (!dm->road_cdf) return fail(TFX_EINVAL, "demand: road_cdf is null");
+  if (mixed && !row_cdf) return fail(TFX_EINVAL, "demand: row_cdf is null");
+  const int K = dm->n_profiles, S = dm->n_segments, n_cdf = dm->n_cdf;
+  if (K < 1 || K > DEMAND_MAX_PROFILES) return fail(TFX_EINVAL, "demand: n_profiles %d is outside 1..%d", K, DEMAND_MAX_PROFILES);
+  if (S < 1 || S > DEMAND_MAX_SEGMENTS) return fail(TFX_EINVAL, "demand: n_segments %d is outside 1..%d", S, DEMAND_MAX_SEGMENTS);
+  if (dm->seg_ticks < 1) return fail(TFX_EINVAL, "demand: seg_ticks %d is below 1", dm->seg_ticks);
+  if (n_cdf < 1 || n_cdf > DEMAND_MAX_CDF) return fail(TFX_EINVAL, "demand: n_cdf %d is outside 1..%d", n_cdf, DEMAND_MAX_CDF);
+  if ((long long)S * dm->seg_ticks > 0x7fffffffLL)
+    return fail(TFX_EINVAL, "demand: the period n_segments * seg_ticks = %lld does not fit an int32", (long long)S * dm->seg_ticks);
+  for (int ks = 0; ks < K * S; ++ks)
+    if (const int c = bad_cdf_row(dm->count_cdf + (size_t)ks * n_cdf, n_cdf))
+      return fail(TFX_EINVAL, c < n_cdf ? "demand: count_cdf row (%d, %d) decreases at %d" : "demand: count_cdf row (%d, %d) does not end in 0xFFFFFFFF",
+                  ks / S, ks % S, c);
+  if (int rc = check_handle(h, false)) return rc;
+  Dev &d = h->d;
+  if (h->het && !mixed)
+    return fail(TFX_EINVAL, "demand: heterogeneous handles (tfx_config.n_archetypes) are not supported - rule 4 draws no archetype rows: "
+                            "tfx_set_demand_mixed draws them (rule 5)");
+  if (mixed && !h->het)
+    return fail(TFX_EINVAL, "demand: tfx_set_demand_mixed needs a heterogeneous handle (tfx_config.n_archetypes); this one has a "
+                            "single archetype: tfx_set_demand");
+  if (mixed && n_rows != h->n_arch)
+    return fail(TFX_EINVAL, "demand: n_rows %d is not the handle's n_archetypes %d", n_rows, h->n_arch);
+  if (d.n_entry < 1) return fail(TFX_EINVAL, "demand: no entry roads");
+  if (d.n_entry > DEMAND_MAX_ENTRY) return fail(TFX_EINVAL, "demand: more than %d entry roads", DEMAND_MAX_ENTRY);
+  const int ne = d.n_entry;
+  for (int ks = 0; ks < K * S; ++ks)
+    if (const int c = bad_cdf_row(dm->road_cdf + (size_t)ks * ne, ne))
+      return fail(TFX_EINVAL, c < ne ? "demand: road_cdf row (%d, %d) decreases at %d" : "demand: road_cdf row (%d, %d) does not end in 0xFFFFFFFF",
+                  ks / S, ks % S, c);
+  for (int ks = 0; mixed && ks < K * S; ++ks)
+    if (const int c = bad_cdf_row(row_cdf + (size_t)ks * n_rows, n_rows))
+      return fail(TFX_EINVAL, c < n_rows ? "demand: row_cdf row (%d, %d) decreases at %d" : "demand: row_cdf row (%d, %d) does not end in 0xFFFFFFFF",
+                  ks / S, ks % S, c);
+  if (int rc = check_handle(h, true)) return rc;
+  const size_t n_cc = (size_t)K * S * n_cdf, n_rc = (size_t)K * S * ne, n_rw = mixed ? (size_t)K * S * n_rows : 0;
+  // rule 5 keeps S rows per road and tick: no road takes more than C - 2 cars in a tick, no env receives more than n_cdf - 1
+  const int per_road = mixed ? (d.C - 2 < n_cdf - 1 ? d.C - 2 : n_cdf - 1) : 0;
+  ArrivalStream s;
+  if (int rc = stage_stream(h, STREAM_DEMAND, dm->seed, {{dm->count_cdf, n_cc}, {dm->road_cdf, n_rc}, {row_cdf, n_rw}}, &s, per_road))
+    return rc;
+  s.count_cdf.assign(dm->count_cdf, dm->count_cdf + n_cc);
+  s.road_cdf.assign(dm->road_cdf, dm->road_cdf + n_rc);
+  DemandDev &m = s.dm;
+  m.count_cdf = s.tables;
+  m.road_cdf = s.tables + n_cc;
+  m.profile = dm->profile_of_env;
+  m.K = K; m.S = S; m.seg_ticks = dm->seg_ticks; m.tick_offset = dm->tick_offset; m.n_cdf = n_cdf;
+  if (mixed) {
+    s.row_cdf.assign(row_cdf, row_cdf + n_rw);
+    s.drow.row_cdf = s.tables + n_cc + n_rc;
+    s.drow.n_rows = n_rows;
+    s.drow.S = per_road;
+  }
+  install_stream(h, std::move(s));
+  return TFX_OK;
 }
 
 // The ticks of a call under an arrival stream whose rows are drawn up front: in chunks of the rows the count buffer
@@ -702,52 +776,10 @@ int tfx_set_regular(tfx_handle h, int32_t every, int32_t burst, uint64_t seed) {
   return TFX_OK;
 }
 
-int tfx_set_demand(tfx_handle h, const tfx_demand *dm) {
-  // (the arguments first, as tfx_road_cells checks them: each cause is named whatever state the handle is in)
-  if (!dm) return fail(TFX_EINVAL, "demand: dm is null");
-  if (!dm->count_cdf) return fail(TFX_EINVAL, "demand: count_cdf is null");
-  if (!dm->road_cdf) return fail(TFX_EINVAL, "demand: road_cdf is null");
-  const int K = dm->n_profiles, S = dm->n_segments, n_cdf = dm->n_cdf;
-  if (K < 1 || K > DEMAND_MAX_PROFILES) return fail(TFX_EINVAL, "demand: n_profiles %d is outside 1..%d", K, DEMAND_MAX_PROFILES);
-  if (S < 1 || S > DEMAND_MAX_SEGMENTS) return fail(TFX_EINVAL, "demand: n_segments %d is outside 1..%d", S, DEMAND_MAX_SEGMENTS);
-  if (dm->seg_ticks < 1) return fail(TFX_EINVAL, "demand: seg_ticks %d is below 1", dm->seg_ticks);
-  if (n_cdf < 1 || n_cdf > DEMAND_MAX_CDF) return fail(TFX_EINVAL, "demand: n_cdf %d is outside 1..%d", n_cdf, DEMAND_MAX_CDF);
-  if ((long long)S * dm->seg_ticks > 0x7fffffffLL)
-    return fail(TFX_EINVAL, "demand: the period n_segments * seg_ticks = %lld does not fit an int32", (long long)S * dm->seg_ticks);
-  // a table row: non-decreasing thresholds, the last one 0xFFFFFFFF (k_demand's binary search relies on the order)
-  auto bad_row = [](const uint32_t *row, int n) {
-    for (int c = 1; c < n; ++c)
-      if (row[c] < row[c - 1]) return c;
-    return row[n - 1] != 0xFFFFFFFFu ? n : 0;
-  };
-  for (int ks = 0; ks < K * S; ++ks)
-    if (const int c = bad_row(dm->count_cdf + (size_t)ks * n_cdf, n_cdf))
-      return fail(TFX_EINVAL, c < n_cdf ? "demand: count_cdf row (%d, %d) decreases at %d" : "demand: count_cdf row (%d, %d) does not end in 0xFFFFFFFF",
-                  ks / S, ks % S, c);
-  if (int rc = check_handle(h, false)) return rc;
-  Dev &d = h->d;
-  if (h->het)
-    return fail(TFX_EINVAL, "demand: heterogeneous handles (tfx_config.n_archetypes) are not supported - rule 4 draws no archetype rows");
-  if (d.n_entry < 1) return fail(TFX_EINVAL, "demand: no entry roads");
-  if (d.n_entry > DEMAND_MAX_ENTRY) return fail(TFX_EINVAL, "demand: more than %d entry roads", DEMAND_MAX_ENTRY);
-  const int ne = d.n_entry;
-  for (int ks = 0; ks < K * S; ++ks)
-    if (const int c = bad_row(dm->road_cdf + (size_t)ks * ne, ne))
-      return fail(TFX_EINVAL, c < ne ? "demand: road_cdf row (%d, %d) decreases at %d" : "demand: road_cdf row (%d, %d) does not end in 0xFFFFFFFF",
-                  ks / S, ks % S, c);
-  if (int rc = check_handle(h, true)) return rc;
-  const size_t n_cc = (size_t)K * S * n_cdf, n_rc = (size_t)K * S * ne;
-  ArrivalStream s;
-  if (int rc = stage_stream(h, STREAM_DEMAND, dm->seed, {{dm->count_cdf, n_cc}, {dm->road_cdf, n_rc}}, &s)) return rc;
-  s.count_cdf.assign(dm->count_cdf, dm->count_cdf + n_cc);
-  s.road_cdf.assign(dm->road_cdf, dm->road_cdf + n_rc);
-  DemandDev &m = s.dm;
-  m.count_cdf = s.tables;
-  m.road_cdf = s.tables + n_cc;
-  m.profile = dm->profile_of_env;
-  m.K = K; m.S = S; m.seg_ticks = dm->seg_ticks; m.tick_offset = dm->tick_offset; m.n_cdf = n_cdf;
-  install_stream(h, std::move(s));
-  return TFX_OK;
+int tfx_set_demand(tfx_handle h, const tfx_demand *dm) { return set_demand(h, dm, false, nullptr, 0); }
+
+int tfx_set_demand_mixed(tfx_handle h, const tfx_demand *dm, const uint32_t *row_cdf, int32_t n_rows) {
+  return set_demand(h, dm, true, row_cdf, n_rows);
 }
 
 int tfx_demand_counts(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *out, void *stream) {
@@ -757,7 +789,28 @@ int tfx_demand_counts(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *out
   if (!h->stream.upfront()) return fail(TFX_ESTATE, "demand: tfx_set_demand has not been called (or another spawn rule replaced it)");
   if (n_ticks == 0) return TFX_OK;
   // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
-  return launch_demand(h, 0, tick0, n_ticks, out, (hipStream_t)stream);
+  return launch_demand(h, 0, tick0, n_ticks, out, nullptr, (hipStream_t)stream);
+}
+
+int tfx_demand_rows(tfx_handle h, int32_t tick0, int32_t n_ticks, int32_t *counts, uint8_t *rows, void *stream) {
+  if (!counts) return fail(TFX_EINVAL, "demand: counts is null");
+  if (!rows) return fail(TFX_EINVAL, "demand: rows is null");
+  if (n_ticks < 0) return fail(TFX_EINVAL, "demand: n_ticks %d is negative", n_ticks);
+  if (int rc = check_handle(h, true)) return rc;
+  if (!h->stream.mixed())
+    return fail(TFX_ESTATE, "demand: tfx_set_demand_mixed has not been called (or another spawn rule replaced it)");
+  if (n_ticks == 0) return TFX_OK;
+  // Not counted by tfx_debug_fail_after, nothing in the handle changes: captured graphs stay valid.
+  return launch_demand(h, 0, tick0, n_ticks, counts, h->stream.drow.S > 0 ? rows : nullptr, (hipStream_t)stream);
+}
+
+int tfx_demand_rows_per_road(tfx_handle h, int32_t *per_road) {
+  if (!per_road) return fail(TFX_EINVAL, "demand: per_road is null");
+  if (int rc = check_handle(h, true)) return rc;
+  if (!h->stream.mixed())
+    return fail(TFX_ESTATE, "demand: tfx_set_demand_mixed has not been called (or another spawn rule replaced it)");
+  *per_road = h->stream.drow.S;
+  return TFX_OK;
 }
 
 int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
@@ -1022,8 +1075,9 @@ int streams_compatible(tfx_handle dst, tfx_handle src) {
     if (p.K != q.K || p.S != q.S || p.seg_ticks != q.seg_ticks || p.n_cdf != q.n_cdf)
       return fail(TFX_EINVAL, "clone: the handles differ in the demand sizes (n_profiles, n_segments, seg_ticks, n_cdf)");
     if (p.tick_offset != q.tick_offset) return fail(TFX_EINVAL, "clone: the handles differ in the demand tick_offset");
-    if (a.count_cdf != b.count_cdf || a.road_cdf != b.road_cdf)
-      return fail(TFX_EINVAL, "clone: the handles differ in the demand tables (count_cdf / road_cdf)");
+    // (a mixed and a plain demand handle: one row_cdf is empty - and same_world refused them before: n_archetypes)
+    if (a.count_cdf != b.count_cdf || a.road_cdf != b.road_cdf || a.row_cdf != b.row_cdf)
+      return fail(TFX_EINVAL, "clone: the handles differ in the demand tables (count_cdf / road_cdf / row_cdf)");
     return TFX_OK;
   }
   if (!a.drawn() || !b.drawn())

@@ -197,18 +197,27 @@ int launch_poisson(tfx_handle h, int n_ticks, hipStream_t st) {
 }
 
 // Rule 4's rows for n_ticks clock ticks into `out` - from the device clock on (use_clock: the rows of a call about to
-// be enqueued on st) or from tick0 on (the preview).  One launch; it writes nothing but `out`.
-int launch_demand(tfx_handle h, int use_clock, int tick0, int n_ticks, int *out, hipStream_t st) {
+// be enqueued on st) or from tick0 on (the preview).  rows: rule 5's archetype rows of those cars as well (a mixed
+// demand), [n_ticks][E][n_entry][S].  One launch; it writes nothing but `out` and `rows`.
+int launch_demand(tfx_handle h, int use_clock, int tick0, int n_ticks, int *out, uint8_t *rows, hipStream_t st) {
   const size_t lds = (size_t)4 * 2 * h->d.n_entry * sizeof(unsigned);
   const long grid = item_grid(h, (long)n_ticks * h->d.E);  // a wavefront per (tick row, env)
-  hipLaunchKernelGGL(k_demand, dim3((unsigned)grid), dim3(256), lds, st, h->d, h->stream.dm, use_clock, tick0, n_ticks, out);
+  const ArrivalStream &s = h->stream;
+  if (rows)
+    hipLaunchKernelGGL(k_demand<true>, dim3((unsigned)grid), dim3(256), lds, st, h->d, s.dm, use_clock, tick0, n_ticks, out,
+                       s.drow, rows);
+  else
+    hipLaunchKernelGGL(k_demand<false>, dim3((unsigned)grid), dim3(256), lds, st, h->d, s.dm, use_clock, tick0, n_ticks, out,
+                       s.drow, rows);
   HIPCHK(hipGetLastError());
   return TFX_OK;
 }
 
-// The stream's next n_rows rows into its count buffer, in one launch: rule 4 from the device clock on
+// The stream's next n_rows rows into its count buffer, in one launch: rule 4 (a mixed demand: and rule 5, into the
+// stream's archetype rows) from the device clock on
 int launch_stream(tfx_handle h, int n_rows, hipStream_t st) {
-  return h->stream.upfront() ? launch_demand(h, 1, 0, n_rows, h->stream.counts, st) : launch_poisson(h, n_rows, st);
+  const ArrivalStream &s = h->stream;
+  return s.upfront() ? launch_demand(h, 1, 0, n_rows, s.counts, s.mixed() ? s.prow.rows : nullptr, st) : launch_poisson(h, n_rows, st);
 }
 
 // The arrivals of a tick are produced by a launch between the ticks: a stream with a position, outside tfx_step's

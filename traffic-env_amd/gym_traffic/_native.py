@@ -96,6 +96,9 @@ _PROTOS = {
     "tfx_set_spawn_archetypes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "tfx_set_demand": (C.c_int, [C.c_void_p, C.POINTER(TfxDemand)]),
     "tfx_demand_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "tfx_set_demand_mixed": (C.c_int, [C.c_void_p, C.POINTER(TfxDemand), C.c_void_p, C.c_int32]),
+    "tfx_demand_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfx_demand_rows_per_road": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "tfx_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "tfx_move_cars": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tfx_advance_finished_cars": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -232,7 +232,7 @@ class TfxEngine(object):
         self.ep_return = self.ep_len = self.final_return = self.final_len = self.truncated = self.ep_index = None
         self.episode_pool = None    # the engine restarts clone from (set_episode_pool)
         # demand profiles (set_demand): None while another spawn rule is bound
-        self.demand = self.demand_profile = self.demand_tables = None
+        self._clear_demand()
         # views with the reference's attribute names (traffic_env.py:372-376)
         self.passed = self.obs[:, :r]
         self.detected = self.obs[:, r:2 * r]
@@ -647,7 +647,7 @@ class TfxEngine(object):
         cdf = gap_table(cars_per_tick)
         nat.check(self.lib.tfx_set_poisson(self.h, float(cars_per_tick), int(seed),
                                            cdf.ctypes.data_as(C.c_void_p), int(cdf.size)))
-        self.demand = self.demand_profile = self.demand_tables = None
+        self._clear_demand()
         self._spawn_bound = None
         self._rows_buf, self._rows_key = None, None
 
@@ -658,21 +658,35 @@ class TfxEngine(object):
         import math
         every, burst = round(1 / cars_per_tick), math.ceil(cars_per_tick)
         nat.check(self.lib.tfx_set_regular(self.h, int(every), int(burst), int(seed)))
-        self.demand = self.demand_profile = self.demand_tables = None
+        self._clear_demand()
         self._spawn_bound = None
         self._rows_buf, self._rows_key = None, None   # (heterogeneous cars: every car is row 0, traffic_env.py:174)
 
-    def set_demand(self, means, weights=None, seg_ticks=1, tick_offset=0, seed=0, profile_of_env=None, n_cdf=None):
+    def _clear_demand(self):
+        """No demand is bound (any more): what set_demand exposes goes"""
+        self.demand = self.demand_profile = self.demand_tables = None
+        self.demand_row_cdf = self.demand_rows_per_road = None
+
+    def set_demand(self, means, weights=None, seg_ticks=1, tick_offset=0, seed=0, profile_of_env=None, n_cdf=None,
+                   row_weights=None):
         """Demand profiles on the device (tfx_set_demand, rule 4 of include/tfx.h): a true per-tick Poisson process whose
         mean changes over time, weighs the entry roads and differs from env to env.  means: [K][S] cars per env per tick
         of profile k in segment s (K <= 16, S <= 64 segments of seg_ticks ticks; the clock tick t is in segment
         floormod(t + tick_offset, S * seg_ticks) // seg_ticks); weights: [K][S][n_entry] (or [n_entry]) weights of the
         entry roads in entry-index order, None: equal.  profile_of_env: int32 [E] device tensor, read whenever arrivals
         are drawn - rewrite it between calls at will; None: one of zeros is made.  It is exposed as `demand_profile`, the
-        tables as `demand_tables` (devrng.demand_counts mirrors the rule from them).  Replaces any earlier spawn rule."""
-        from gym_traffic.devrng import demand_tables
+        tables as `demand_tables` (devrng.demand_counts mirrors the rule from them).  Replaces any earlier spawn rule.
+        Heterogeneous cars (an archetype table): every car's row is drawn as well (tfx_set_demand_mixed, rule 5), by
+        row_weights [K][S][n_archetypes] (or [n_archetypes]; None: equal) - the truck share of profile k in segment s;
+        the table is exposed as `demand_row_cdf`, the rows kept per road and tick as `demand_rows_per_road`
+        (devrng.demand_rows mirrors the rule from them).  A single-archetype engine takes no row_weights."""
+        from gym_traffic.devrng import demand_row_table, demand_tables
+        if row_weights is not None and not self.het:
+            raise ValueError("row_weights need an engine with an archetype table (archetypes=)")
         tables = demand_tables(means, weights, n_cdf=n_cdf, n_entry=self.n_entry)
         K, S, n = tables.count_cdf.shape
+        n_arch = max(1, int(self.cfg.n_archetypes))
+        row_cdf = np.ascontiguousarray(demand_row_table(row_weights, K, S, n_arch), np.uint32) if self.het else None
         if profile_of_env is None:
             profile_of_env = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
         prof = profile_of_env
@@ -686,9 +700,17 @@ class TfxEngine(object):
         dm.count_cdf, dm.road_cdf = cc.ctypes.data_as(C.c_void_p), rc.ctypes.data_as(C.c_void_p)
         dm.profile_of_env = _ptr(prof)
         dm.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        per_road = C.c_int32()
         with torch.cuda.device(self.device):
-            nat.check(self.lib.tfx_set_demand(self.h, C.byref(dm)))
+            if row_cdf is None:
+                nat.check(self.lib.tfx_set_demand(self.h, C.byref(dm)))
+            else:
+                nat.check(self.lib.tfx_set_demand_mixed(self.h, C.byref(dm), row_cdf.ctypes.data_as(C.c_void_p), n_arch))
+                nat.check(self.lib.tfx_demand_rows_per_road(self.h, C.byref(per_road)))
+        self._clear_demand()
         self.demand_profile, self.demand_tables = prof, tables
+        if row_cdf is not None:
+            self.demand_row_cdf, self.demand_rows_per_road = row_cdf, int(per_road.value)
         self.demand = dict(seg_ticks=int(seg_ticks), tick_offset=int(tick_offset), seed=int(seed))
         self._spawn_bound = None
         self._rows_buf, self._rows_key = None, None
@@ -707,6 +729,32 @@ class TfxEngine(object):
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_demand_counts(self.h, int(tick0), int(n_ticks), _ptr(out), self._stream()))
         return out
+
+    def demand_rows(self, tick0, n_ticks, out=None):
+        """(counts int32 [n_ticks, E, n_entry], rows uint8 [n_ticks, E, n_entry, demand_rows_per_road]) device tensors:
+        rules 4 and 5 for clock ticks tick0 .. tick0 + n_ticks - 1 under the demand_profile as it stands
+        (tfx_demand_rows: one read-only launch, no host synchronisation) - what devrng.demand_rows computes on the host
+        for j < min(count, demand_rows_per_road); the entries past a road's cars are 0 here too (the tensor starts as
+        zeros, the launch leaves them alone).  out: the caller's (counts, rows) pair of those shapes, rows as the caller
+        left them past the cars.  TfxError -2 without a demand that draws rows."""
+        if self.demand_rows_per_road is None:
+            raise nat.TfxError("tfx error -2: demand: no demand that draws archetype rows is bound (set_demand on an "
+                               "engine with an archetype table)")
+        shape = (int(n_ticks), self.E, self.n_entry, self.demand_rows_per_road)
+        if out is None:
+            counts = torch.empty(shape[:3], dtype=torch.int32, device=self.device)
+            rows = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        else:
+            counts, rows = out
+            if counts.dtype != torch.int32 or tuple(counts.shape) != shape[:3] or rows.dtype != torch.uint8 or tuple(rows.shape) != shape \
+                    or not (counts.is_cuda and rows.is_cuda and counts.is_contiguous() and rows.is_contiguous()):
+                raise ValueError("demand_rows(out=): contiguous device tensors int32 [%d, %d, %d] and uint8 [%d, %d, %d, %d]"
+                                 % (shape[:3] + shape))
+        if rows.numel() == 0:           # (no ticks, or n_cdf = 1: no cars at all - an empty tensor has no address)
+            return self.demand_counts(tick0, n_ticks, out=counts), rows
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_demand_rows(self.h, int(tick0), int(n_ticks), _ptr(counts), _ptr(rows), self._stream()))
+        return counts, rows
 
     def set_greedy(self, spacing=3):
         """On-device greedy controller (algorithms/greedy.py:14-16), a decision every `spacing` ticks."""
@@ -764,7 +812,7 @@ class TfxEngine(object):
         if period is not None:
             key = ("periodic", int(period))
             if self._spawn_bound != key:
-                self.demand = self.demand_profile = self.demand_tables = None
+                self._clear_demand()
                 nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_PERIODIC, None, int(period), 0))
                 self._spawn_bound = key
         elif counts is not None:
@@ -780,11 +828,11 @@ class TfxEngine(object):
                 key = ("held", c.data_ptr())
             self._spawn_buf = c
             if self._spawn_bound != key:
-                self.demand = self.demand_profile = self.demand_tables = None
+                self._clear_demand()
                 nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_COUNTS, _ptr(c), 0, 1 if per_tick else 0))
                 self._spawn_bound = key
         elif self._spawn_bound != ("none",):
-            self.demand = self.demand_profile = self.demand_tables = None
+            self._clear_demand()
             nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_NONE, None, 0, 0))
             self._spawn_bound = ("none",)
 
@@ -859,7 +907,7 @@ class TfxEngine(object):
             self._action_bound = ka
         ks = ("per_tick" if per_tick else "held", c.data_ptr())
         if self._spawn_bound != ks:
-            self.demand = self.demand_profile = self.demand_tables = None
+            self._clear_demand()
             nat.check(self.lib.tfx_set_spawns(self.h, nat.SPAWN_COUNTS, _ptr(c), 0, 1 if per_tick else 0))
             self._spawn_bound = ks
         self._action_buf, self._spawn_buf = a, c

@@ -23,7 +23,8 @@ road, and the finished trips of every env's log reduced from a cursor on.
 `demand_tables`, `demand_segment` and `demand_counts` belong to the demand profiles (tfx_set_demand, rule 4 of
 include/tfx.h): the threshold tables the device reads, the segment of a clock tick, and the rule itself in NumPy - a pure
 function of (seed, stream id, clock tick), with no state to carry: a true per-tick Poisson process, not the reference's
-rounded-gap generator that PoissonMirror mirrors.
+rounded-gap generator that PoissonMirror mirrors.  `demand_row_table` and `demand_rows` add rule 5 (tfx_set_demand_mixed): the
+third threshold table, and the archetype row of every one of those cars in creation order per road.
 """
 import collections
 import math
@@ -36,6 +37,7 @@ TAG_GAP, TAG_ROAD, TAG_ARCH = 0x47415021, 0x524F4144, 0x41524348
 TAG_EPISODE = 0x45504953
 TAG_POOL = 0x504F4F4C
 TAG_DCNT, TAG_DROAD = 0x44434E54, 0x44524F44
+TAG_DROW = 0x44524F57
 MASK = 0xFFFFFFFF
 
 
@@ -613,12 +615,44 @@ def demand_segment(ticks, n_segments, seg_ticks=1, tick_offset=0):
     return (np.mod(t, np.int64(int(n_segments) * int(seg_ticks))) // np.int64(seg_ticks)).astype(np.int64)
 
 
+def demand_row_table(row_weights, K, S, n_rows):
+    """The third host table of tfx_set_demand_mixed -> row_cdf uint32 [K, S, n_rows]: the cumulative weights of the
+    archetype-table rows of profile k in segment s, scaled by 2^32, the last entry of every row 0xFFFFFFFF (the format of
+    DemandTables.road_cdf).  row_weights: [K][S][n_rows] (or [n_rows], for every profile and segment) non-negative
+    weights; None: equal weights.  A row of weight zero is not drawn (a LAST row of weight zero: for one v in 2^32)."""
+    K, S, n_rows = int(K), int(S), int(n_rows)
+    if not 1 <= n_rows <= 64:
+        raise ValueError("n_rows must be in 1..64")
+    w = np.ones(n_rows) if row_weights is None else np.asarray(row_weights, np.float64)
+    if w.ndim == 1:
+        w = np.broadcast_to(w, (K, S, w.shape[0]))
+    if w.shape != (K, S, n_rows):
+        raise ValueError("row_weights must be [%d][%d][%d] (or [%d])" % (K, S, n_rows, n_rows))
+    if not np.all(np.isfinite(w)) or (w < 0).any() or (w.sum(axis=-1) <= 0).any():
+        raise ValueError("row_weights must be finite, >= 0, and not all zero in any row")
+    return _thresholds(np.cumsum(w, axis=-1) / w.sum(axis=-1, keepdims=True))
+
+
 def demand_counts(seed, stream_ids, ticks, tables, profile_of_env=None, seg_ticks=1, tick_offset=0):
     """Rule 4 of include/tfx.h in NumPy -> int32 [T, E, n_entry]: the cars env e (stream id stream_ids[e]: its global env
     id, or its source's after a clone with its stream) receives on each entry road in clock tick ticks[t] (an int32 clock
     value; anything else wraps to one, as the device clock does).  tables: a
     DemandTables; profile_of_env: int [E] (None: profile 0; outside [0, K): no cars).  A pure function of its arguments:
     any subset of envs or ticks, in any order, gives the same rows."""
+    return _demand(seed, stream_ids, ticks, tables, profile_of_env, seg_ticks, tick_offset)
+
+
+def demand_rows(seed, stream_ids, ticks, tables, row_cdf, per_road, profile_of_env=None, seg_ticks=1, tick_offset=0):
+    """Rules 4 and 5 of include/tfx.h in NumPy -> (counts int32 [T, E, n_entry] - demand_counts' -, rows uint8 [T, E,
+    n_entry, per_road]): rows[t, e, ej, j] is the archetype-table row of the j-th car, in car-index order, that env e
+    receives on entry road ej in clock tick ticks[t], for j < min(count, per_road); 0 past it.  row_cdf: uint32 [K, S,
+    n_rows] (demand_row_table); per_road: the S of rule 5, min(capacity - 2, n_cdf - 1) on the device.  Pure, like
+    demand_counts: any subset of envs or ticks, in any order, gives the same rows."""
+    return _demand(seed, stream_ids, ticks, tables, profile_of_env, seg_ticks, tick_offset, row_cdf, int(per_road))
+
+
+def _demand(seed, stream_ids, ticks, tables, profile_of_env, seg_ticks, tick_offset, row_cdf=None, per_road=0):
+    """demand_counts (row_cdf None) or demand_rows"""
     count_cdf, road_cdf = [np.asarray(a, np.uint32).astype(np.uint64) for a in tables]
     K, S, n_cdf = count_cdf.shape
     ne = road_cdf.shape[2]
@@ -631,8 +665,17 @@ def demand_counts(seed, stream_ids, ticks, tables, profile_of_env=None, seg_tick
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     k0, k1 = seed & MASK, seed >> 32
     out = np.zeros((T, E, ne), np.int32)
+    arch = None
+    if row_cdf is not None:
+        row_cdf = np.asarray(row_cdf, np.uint32).astype(np.uint64)
+        if row_cdf.ndim != 3 or row_cdf.shape[:2] != (K, S) or per_road < 0:
+            raise ValueError("row_cdf must be [K][S][n_rows] for the tables' K and S, per_road >= 0")
+        n_rows = row_cdf.shape[2]
+        row_rows = row_cdf.reshape(K * S, n_rows)
+        arch = np.zeros((T, E, ne, per_road), np.uint8)
+    ret = (lambda: out) if arch is None else (lambda: (out, arch))
     if T == 0 or E == 0:
-        return out
+        return ret()
     valid = (prof >= 0) & (prof < K)
     k = np.where(valid, prof, 0)
     seg = demand_segment(t, S, seg_ticks, tick_offset)
@@ -642,12 +685,12 @@ def demand_counts(seed, stream_ids, ticks, tables, profile_of_env=None, seg_tick
     rows = count_cdf[k[None, :], seg[:, None]]                       # [T, E, n_cdf]
     N = (u0[..., None] >= rows[..., :n_cdf - 1]).sum(axis=-1)
     N = np.where(valid[None, :], N, 0).reshape(-1)
-    if ne == 1:
+    if ne == 1 and arch is None:
         out.reshape(-1)[:] = N
         return out
     item = np.repeat(np.arange(T * E), N)
     if item.size == 0:
-        return out
+        return ret()
     c = np.arange(item.size) - np.repeat(np.cumsum(N) - N, N)      # car index within its item
     flat = out.reshape(-1)
     ks = (k[None, :] * S + seg[:, None]).reshape(-1)
@@ -657,5 +700,21 @@ def demand_counts(seed, stream_ids, ticks, tables, profile_of_env=None, seg_tick
         words = philox4x32_words(tw.reshape(-1)[it], gw.reshape(-1)[it], TAG_DROAD, cc >> 2, k0, k1)
         w = np.choose(cc & 3, words)
         ej = (w[:, None] >= road_rows[ks[it]][:, :ne - 1]).sum(axis=1)
-        flat += np.bincount(it * ne + ej, minlength=flat.size).astype(np.int32)
-    return out
+        road = it * ne + ej
+        if arch is not None and per_road > 0:
+            # rule 5.  The cars of the chunk stand in (item, car index) order: a stable sort by road keeps the car-index
+            # order within a road; the cars of the chunks before are in `flat` already
+            order = np.argsort(road, kind="stable")
+            sr = road[order]
+            first = np.nonzero(np.r_[True, sr[1:] != sr[:-1]])[0]
+            run = np.diff(np.r_[first, sr.size])
+            j = np.empty(sr.size, np.int64)
+            j[order] = np.arange(sr.size) - np.repeat(first, run)
+            j += flat[road]
+            words = philox4x32_words(tw.reshape(-1)[it], gw.reshape(-1)[it], TAG_DROW, cc >> 2, k0, k1)
+            v = np.choose(cc & 3, words)
+            row = (v[:, None] >= row_rows[ks[it]][:, :n_rows - 1]).sum(axis=1)
+            keep = j < per_road
+            arch.reshape(-1)[road[keep] * per_road + j[keep]] = row[keep].astype(np.uint8)
+        flat += np.bincount(road, minlength=flat.size).astype(np.int32)
+    return ret()

@@ -11,14 +11,16 @@ counts per tick, entry roads from the same Philox streams), from the on-device f
 from demand profiles on the device (`spawn='demand'`, rule 4 of include/tfx.h: a true per-tick Poisson process - not the
 reference's rounded-gap generator - whose mean changes over time, weighs the entry roads and differs from env to env:
 `demand=dict(means=[K][S], weights=[K][S][n_entry] or None, seg_ticks=, tick_offset=0)`, the profile of every env in the
-device tensor `demand_profile`, int32 [E], zeros at first and the user's to rewrite between calls).
+device tensor `demand_profile`, int32 [E], zeros at first and the user's to rewrite between calls; with `archetypes` the
+dict also takes `row_weights=[K][S][n]`, the share of every table row among the cars of profile k in segment s).
 Sharding across GPUs is by env id (gym_traffic/distributed.py); envs share nothing.
 
 Mixed cars: `archetypes` takes the reference's `archetypes` table (traffic_env.py:35-43) as rows (v, l, a, delta, v0, b,
 T, s0) - the order of TfxEngine - and every car the envs make is a row of it, kept through every handoff (planes = 3,
 the transposed layout).  `poisson` replays the reference's `archetypes[random.randint(n)]` per car on each env's
 RandomState (env k equals a single-env TrafficEnv with the same table seeded `seed + k`); `device` draws the rows on the
-device by rule 1 of include/tfx.h (gym_traffic/devrng.py mirrors it); `regular`, `regular_device` and `periodic` make
+device by rule 1 of include/tfx.h (gym_traffic/devrng.py mirrors it); `demand` draws them on the device by rule 5, by
+the demand's `row_weights` (devrng.demand_rows mirrors it); `regular`, `regular_device` and `periodic` make
 every car row 0, as the reference's `regular` generator does (traffic_env.py:174).
 
 Episodes: with `autoreset=True` the envs keep their episodes on the device (tfx_set_episodes, include/tfx.h).  Every
@@ -72,7 +74,7 @@ class TrafficVecEnv(object):
         autoreset / episode_len: episodes on the device, see the module docstring (episode_len needs autoreset; in
         validate mode the trip log of an ended episode stays readable until the next decision begins).
         demand: with spawn='demand', the keyword arguments of TfxEngine.set_demand other than the seed - means, weights,
-        seg_ticks, tick_offset, n_cdf (single-archetype envs only).
+        seg_ticks, tick_offset, n_cdf and, with `archetypes`, row_weights (None: every row equally likely).
         trip_cap: validate mode, the trips every env's log holds between two restarts (later ones are counted, not
         kept: travel_times().lost)."""
         if episode_len is not None and not autoreset:
@@ -118,7 +120,7 @@ class TrafficVecEnv(object):
         elif spawn == 'demand':
             if not isinstance(demand, dict) or "means" not in demand:
                 raise ValueError("spawn='demand' needs demand=dict(means=..., weights=..., seg_ticks=..., tick_offset=0)")
-            unknown = set(demand) - {"means", "weights", "seg_ticks", "tick_offset", "n_cdf"}
+            unknown = set(demand) - {"means", "weights", "seg_ticks", "tick_offset", "n_cdf", "row_weights"}
             if unknown:
                 raise ValueError("demand: unknown keys %s" % sorted(unknown))
             eng.set_demand(seed=seed, **demand)
