@@ -15,7 +15,12 @@ Instrumentation (wrappers around reference callables; no reference logic is chan
   * `advance_finished_cars` / `advance_hack` are wrapped to snapshot the state
     between `move_cars` and the advance (the "mid" state) for kernel-level parity.
 
-Usage:  python oracle/gen_golden.py [--only NAME] [--set main|params]
+The third set (--set states, tests/golden/states/) does not start from the empty map: every state of a scenario is a
+reference env whose `state`, `leading`, `lastcar`, `current_phase`, `elapsed` and `steps` are overwritten with a drawn
+ring state of oracle/ring_states.py, stepped for a few ticks with scripted arrivals that go through the reference's own
+add_new_cars.  Wrappers around move_cars, add_car and the advance count the branches the run took (run_states).
+
+Usage:  python oracle/gen_golden.py [--only NAME] [--set main|params|states]
 """
 import argparse
 import json
@@ -27,6 +32,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from ref_loader import load_reference  # noqa: E402
+from ring_states import BEYOND, CROWD, live_slots, random_state, state_rows  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
 
@@ -113,6 +119,260 @@ pscen("three_rows_rate07", L=120.0, C=16, seed=24, rate=0.7, lcps=0.2,
 pscen("constants", L=120.0, C=16, seed=25, lcps=0.3,
       constants=dict(yellow_ticks=4, thresh=0.35, overflow_penalty=7, eps=3e-7))
 REF_CONSTANT_NAMES = dict(yellow_ticks="YELLOW_TICKS", thresh="THRESH", overflow_penalty="OVERFLOW_PENALTY", eps="EPS")
+
+
+# ---- the third list: runs that START from loaded ring states, written to tests/golden/states/ ---------------------------
+# N independent states per scenario, K ticks each, 0-3 scripted arrivals per tick.  State i draws beyond = BEYOND[i % 4],
+# crowd from CROWD, and has sorted x where (i // 4 + i) is even: with N = 8 every `beyond` occurs sorted and unsorted,
+# with N = 4 every `beyond` occurs once.  On top of the family, the head of about one road in seven stands exactly at the
+# road end (x = L, v = 0): the edge of `x > length`.  `ticks`: the clock of every state (60, as in the tests that use the family).
+# Seeds: a seed would be replaced, with a note here, if a 1-ulp float at a threshold flipped an integer of the oracle's
+# free run (tests/test_oracle_states.py); none had to be.
+OUT_STATES = os.path.join(OUT, "states")
+STATE_SCENARIOS = {}
+# tests/test_gpu_archetypes.py:MIXED_ROWS (exponents 4, 1, 2, 8, 2.5, 0.75)
+MIXED_ROWS = [[11.11, 4, 3, 4, 13.89, 6, 2, 1], [8.0, 8, 1.5, 1, 10.0, 4, 2.5, 2], [12.0, 3.5, 4, 2, 16.0, 7, 1.5, 1],
+              [9.0, 12, 1.0, 8, 11.0, 3, 3.0, 3], [10.0, 5, 2.5, 2.5, 14.0, 5, 1.8, 1.5], [7.0, 6, 2.0, 0.75, 9.0, 4, 2.2, 2]]
+
+
+def sscen(name, **kw):
+    d = dict(m=2, n=2, L=60.0, C=10, seed=0, N=8, K=6, rate=0.5, learn_switch=False, mode='train', entry='all',
+             archetypes=None, constants=None, ticks=None)
+    d.update(kw)
+    d["ticks"] = list(d["ticks"] or [60] * d["N"])
+    assert len(d["ticks"]) == d["N"]
+    STATE_SCENARIOS[name] = d
+
+
+sscen("st_2x2_c10", seed=101)
+sscen("st_3x2_c20_validate", m=3, n=2, C=20, L=120.0, seed=102, mode='validate')
+sscen("st_2x3_c6_rate1_ls_validate", m=2, n=3, C=6, L=30.0, seed=103, rate=1.0, learn_switch=True, mode='validate')
+sscen("st_2x2_c34_rate07", C=34, L=200.0, seed=104, rate=0.7)
+sscen("st_2x3_c66", m=2, n=3, C=66, L=400.0, seed=105)
+sscen("st_2x2_c130", C=130, L=800.0, seed=106)
+sscen("st_1x1_c258", m=1, n=1, C=258, L=900.0, seed=107)
+# every car a random row; a ninth state at a clock beyond 2^21 (its cars spawned in the last few hundred ticks)
+sscen("st_3x2_c20_rows_validate", m=3, n=2, C=20, L=120.0, seed=108, mode='validate', archetypes=MIXED_ROWS, N=9,
+      ticks=[60] * 8 + [3000000])
+sscen("st_2x2_c16_constants", C=16, L=120.0, seed=109,
+      constants=dict(yellow_ticks=4, thresh=0.35, overflow_penalty=7, eps=3e-7))
+
+TALLIES = ("wrapped_road_ticks", "wrapped_waiting_quirk", "multi_pop_road_ticks", "max_pops", "cascades",
+           "handoffs_refused", "spawns_refused", "full_pop_and_receive", "leaders_at_next_tail", "heads_at_road_end", "trips")
+
+
+def run_states(name, sc, mods):
+    """-> the fixture of one scenario of STATE_SCENARIOS (arrays stacked over its N states)"""
+    te = mods["gym_traffic.envs.traffic_env"]
+    rg = mods["gym_traffic.envs.roadgraph"]
+    gym = mods["gym"]
+    args = mods["args"]
+
+    te.CAPACITY = C = int(sc["C"])
+    args.update_flags(poisson=True, rate=float(sc["rate"]), local_cars_per_sec=0.12, entry=sc["entry"],
+                      learn_switch=bool(sc["learn_switch"]), mode=sc["mode"])
+    xi, vi, wi = te.xi, te.vi, te.wi
+    keep_archetypes = te.archetypes
+    keep_constants = {ref: getattr(te, ref) for ref in REF_CONSTANT_NAMES.values()}
+    for k, val in (sc.get("constants") or {}).items():
+        setattr(te, REF_CONSTANT_NAMES[k], val)
+    arch_cols = [te.vi, te.li, te.ai, te.deltai, te.v0i, te.bi, te.ti, te.s0i]
+    if sc.get("archetypes"):
+        tab = np.zeros((len(sc["archetypes"]), te.params), np.float32)
+        tab[:, arch_cols] = np.asarray(sc["archetypes"], np.float32)
+        te.archetypes = tab
+    n_rows = te.archetypes.shape[0]
+    key_cols = arch_cols[1:]
+
+    def row_plane(state):
+        """row of te.archetypes each slot's car equals in everything but x, v, w (0 where none does)"""
+        out = np.zeros((state.shape[0], state.shape[2]), np.int8)
+        for a in range(n_rows):
+            out[(state[:, key_cols, :] == te.archetypes[a, key_cols][None, :, None]).all(axis=1)] = a
+        return out
+
+    road_length = float(sc["L"])
+    tally = dict.fromkeys(TALLIES, 0)
+    phase_of = ["idle"]          # "spawn" inside add_new_cars, "advance" inside the advance
+    received = set()             # roads that took a handed-off car in the current advance
+    orig_add_car, orig_adv, orig_hack, orig_move = te.add_car, te.advance_finished_cars, te.advance_hack, te.move_cars
+
+    def counted_add_car(road, car, state, leading, lastcar, rewards, dests):
+        if phase_of[0] == "advance" and car[xi] > road_length:
+            tally["cascades"] += 1          # still beyond the road end after the subtraction of :130
+        refused = orig_add_car(road, car, state, leading, lastcar, rewards, dests)
+        if phase_of[0] == "advance":
+            tally["handoffs_refused"] += int(bool(refused))
+            if not refused:
+                received.add(int(road))
+        elif phase_of[0] == "spawn":
+            tally["spawns_refused"] += int(bool(refused))
+        return refused
+
+    def counted_move(dests, phases, length, nexts, state, leading, lastcar, rate, current_phase, elapsed, *a):
+        wrapped = np.nonzero(leading > lastcar)[0]
+        tally["wrapped_road_ticks"] += len(wrapped)
+        for e, dst in enumerate(dests):        # (the condition of update_lights, :86-90, read - only to count)
+            if dst >= 0 and not (phases[e] == current_phase[dst] or elapsed[dst] < te.YELLOW_TICKS) \
+                    and nexts[e] >= 0 and lastcar[nexts[e]] != leading[nexts[e]]:
+                tally["leaders_at_next_tail"] += 1
+        out = orig_move(dests, phases, length, nexts, state, leading, lastcar, rate, current_phase, elapsed, *a)
+        for e in wrapped:
+            if dests[e] >= 0:                  # :210 counts x < THRESH on the slots 1 .. lastcar, :200 counts v
+                by_x = int((state[e, xi, 1:lastcar[e] + 1] < te.THRESH).sum())
+                by_v = int((state[e, vi, 1:lastcar[e] + 1] < te.THRESH).sum())
+                tally["wrapped_waiting_quirk"] += int(by_x != by_v)
+        return out
+
+    def counted_advance(orig):
+        def f(dests, length, nexts, state, leading, lastcar, *a):
+            before = leading.copy()
+            heads = np.where(leading + 1 < C, leading + 1, 1)
+            tally["heads_at_road_end"] += int(((leading != lastcar) & (state[np.arange(len(leading)), xi, heads] == length)).sum())
+            cars = np.where(leading > lastcar, lastcar + (C - 1) - leading, lastcar - leading)
+            phase_of[0] = "advance"
+            received.clear()
+            try:
+                out = orig(dests, length, nexts, state, leading, lastcar, *a)
+            finally:
+                phase_of[0] = "idle"
+            pops = np.where(leading >= before, leading - before, leading + (C - 1) - before)
+            tally["multi_pop_road_ticks"] += int((pops >= 2).sum())
+            tally["max_pops"] = max(tally["max_pops"], int(pops.max()))
+            tally["full_pop_and_receive"] += sum(1 for e in received if cars[e] == C - 2 and pops[e] > 0)
+            return out
+        return f
+
+    te.add_car = counted_add_car
+    te.move_cars = counted_move
+    te.advance_finished_cars = counted_advance(orig_adv)
+    te.advance_hack = counted_advance(orig_hack)
+    try:
+        N, K = sc["N"], sc["K"]
+        rng = np.random.RandomState(sc["seed"])
+        graph = env = None
+        per_state = []
+        spawn_road, spawn_row, spawn_off, trip_times, trip_off = [], [], [0], [], [0]
+        for i in range(N):
+            env = gym.make('traffic-v0')
+            graph = rg.GridRoad(sc["m"], sc["n"], sc["L"])
+            env.set_graph(graph)
+            env.seed_generator(sc["seed"])
+            env.reset_entrypoints()
+            np.random.seed(sc["seed"])
+            env.state[:] = 0
+            env.rewards[:] = 0
+            env.reset()
+            Iq, r, R = graph.intersections, graph.train_roads, graph.roads
+            tick0 = int(sc["ticks"][i])
+            x, v, w, leading, lastcar = [a[0] for a in random_state(
+                rng, 1, R, C, sc["L"], crowd=rng.choice(CROWD), beyond=BEYOND[i % 4], sorted_x=(i // 4 + i) % 2 == 0)]
+            # what the family does not reach by itself: a standing head exactly AT the road end, which `x > length` (:123)
+            # leaves on its road for as long as its light is red
+            for e in range(R):
+                if lastcar[e] != leading[e] and rng.rand() < 0.15:
+                    h = leading[e] + 1 if leading[e] + 1 < C else 1
+                    x[e, h], v[e, h] = sc["L"], 0.0
+            if tick0 > 400:
+                w = (tick0 - 400 + 8 * w).astype(np.float32)
+            row = rng.randint(0, n_rows, size=x.shape).astype(np.int8) if sc.get("archetypes") else np.zeros(x.shape, np.int8)
+            table = te.archetypes.copy()
+            table[:, wi] = 0
+            env.state[:] = state_rows(x, v, w, leading, lastcar, table, row)
+            env.leading[:] = leading
+            env.lastcar[:] = lastcar
+            env.current_phase[:] = rng.randint(2, size=Iq)
+            env.elapsed[:] = rng.randint(0, 12, size=Iq)
+            env.steps = np.float32(tick0)
+            for a in (env.waiting, env.passed_dst, env.rewards, env.passed, env.detected):
+                a[:] = 0
+            env.trip_times = []
+            acts = rng.randint(2, size=(K, Iq)).astype(np.int32)
+            script_roads = [rng.choice(graph.entrypoints, size=rng.randint(0, 4)).astype(np.int32) for _ in range(K)]
+            script_rows = [rng.randint(0, n_rows, size=len(rd)).astype(np.int32) for rd in script_roads]
+
+            # arrivals go through the reference's own add_new_cars (:274-283): it draws the tick's cars from rand_car
+            # until None and every car's road from rand.choice
+            def cars():
+                for rows_t in script_rows:
+                    for a in rows_t:
+                        yield te.archetypes[a]
+                    yield None
+            roads_flat = iter([int(rd) for rds in script_roads for rd in rds])
+
+            class Roads(object):
+                def choice(self, entrypoints):
+                    rd = next(roads_flat)
+                    assert rd in entrypoints
+                    return rd
+            env.rand_car = cars()
+            env.rand = Roads()
+            orig_add_new = env.add_new_cars
+
+            def add_new(tick, orig_add_new=orig_add_new):
+                phase_of[0] = "spawn"
+                try:
+                    return orig_add_new(tick)
+                finally:
+                    phase_of[0] = "idle"
+            env.add_new_cars = add_new
+
+            rec = dict(leading=[], lastcar=[], obs=[], rewards=[], waiting=[], passed_dst=[], leader_x=[], state_x=[],
+                       state_v=[], state_w=[], state_a=[], done=[0], trip_count=[0])
+
+            def record():
+                rec["leading"].append(env.leading.copy())
+                rec["lastcar"].append(env.lastcar.copy())
+                rec["obs"].append(env.obs.copy())
+                rec["rewards"].append(env.rewards.copy())
+                rec["waiting"].append(env.waiting.copy())
+                rec["passed_dst"].append(env.passed_dst.astype(np.uint8))
+                rec["leader_x"].append(env.state[np.arange(R), xi, env.leading].copy())
+                px, pv, pw = live_planes(env.state, env.leading, env.lastcar, C, (xi, vi, wi))
+                live = live_slots(env.leading, env.lastcar, C)
+                assert np.isfinite(px[live]).all() and np.isfinite(pv[live]).all(), (name, i, "a live value is not finite")
+                rec["state_x"].append(px)
+                rec["state_v"].append(pv)
+                rec["state_w"].append(pw)
+                rec["state_a"].append(np.where(live, row_plane(env.state), 0).astype(np.int8))
+            record()
+            assert np.array_equal(rec["state_a"][0], np.where(live_slots(leading, lastcar, C), row, 0))
+            for t in range(K):
+                _, _, d, _ = env.step(acts[t].copy())
+                rec["done"].append(int(bool(d)))
+                rec["trip_count"].append(len(env.trip_times))
+                record()
+                spawn_road.extend(script_roads[t].tolist())
+                spawn_row.extend(script_rows[t].tolist())
+                spawn_off.append(len(spawn_road))
+            assert next(env.rand_car, "end") == "end" and next(roads_flat, "end") == "end"
+            tally["trips"] += len(env.trip_times)
+            trip_times.extend(env.trip_times)
+            trip_off.append(len(trip_times))
+            rec["actions"] = acts
+            per_state.append(rec)
+        out = dict(phases=graph.phases.copy(), dest=graph.dest.copy(), nexts=graph.nexts.copy(),
+                   entrypoints=graph.entrypoints.copy(), ticks=np.asarray(sc["ticks"], np.int64))
+        for k in per_state[0]:
+            out[k] = np.stack([np.asarray(rec[k]) for rec in per_state])          # [N, K + 1 (actions: K), ...]
+        for k in ("leading", "lastcar", "obs", "waiting"):
+            out[k] = out[k].astype(np.int32)
+        out.update(done=out["done"].astype(np.uint8), trip_count=out["trip_count"].astype(np.int64),
+                   spawn_off=np.asarray(spawn_off, np.int64).reshape(-1),       # cars of state i, tick t: [i * K + t]
+                   spawn_road=np.asarray(spawn_road, np.int32), spawn_arch=np.asarray(spawn_row, np.int32),
+                   trip_times=np.asarray(trip_times, np.float64), trip_off=np.asarray(trip_off, np.int64))
+        if sc.get("archetypes"):
+            out["archetypes"] = te.archetypes.copy()
+        for k in TALLIES:
+            out["tally_" + k] = np.int64(tally[k])
+        out["scenario"] = np.array(json.dumps(sc))
+        out["numpy_version"] = np.array(np.__version__)
+        return out
+    finally:
+        te.add_car, te.move_cars, te.advance_finished_cars, te.advance_hack = orig_add_car, orig_move, orig_adv, orig_hack
+        te.archetypes = keep_archetypes
+        for ref, val in keep_constants.items():
+            setattr(te, ref, val)
 
 
 def run(name, sc, mods):
@@ -325,16 +585,25 @@ def live_planes(state, leading, lastcar, C, planes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
-    ap.add_argument("--set", default="all", choices=["all", "main", "params"],
-                    help="main: tests/golden/, params: tests/golden/params/ (the runs off the defaults)")
+    ap.add_argument("--set", default="all", choices=["all", "main", "params", "states"],
+                    help="main: tests/golden/, params: tests/golden/params/ (the runs off the defaults), "
+                         "states: tests/golden/states/ (the runs from loaded ring states)")
     a = ap.parse_args()
     mods = load_reference()
-    todo = [(OUT, n, sc) for n, sc in SCENARIOS.items() if a.set != "params"]
-    todo += [(OUT_PARAMS, n, sc) for n, sc in PARAM_SCENARIOS.items() if a.set != "main"]
+    todo = [(OUT, n, sc) for n, sc in SCENARIOS.items() if a.set in ("all", "main")]
+    todo += [(OUT_PARAMS, n, sc) for n, sc in PARAM_SCENARIOS.items() if a.set in ("all", "params")]
+    todo += [(OUT_STATES, n, sc) for n, sc in STATE_SCENARIOS.items() if a.set in ("all", "states")]
     for folder, name, sc in todo:
         if a.only and a.only != name:
             continue
         os.makedirs(folder, exist_ok=True)
+        if folder == OUT_STATES:
+            out = run_states(name, sc, mods)
+            path = os.path.join(folder, name + ".npz")
+            np.savez_compressed(path, **out)
+            print("%-30s N=%d K=%d %s  %.1f KB" % (name, sc["N"], sc["K"], " ".join(
+                "%s=%d" % (k, int(out["tally_" + k])) for k in TALLIES), os.path.getsize(path) / 1024.0))
+            continue
         out = run(name, sc, mods)
         path = os.path.join(folder, name + ".npz")
         np.savez_compressed(path, **out)

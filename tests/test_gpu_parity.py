@@ -16,6 +16,7 @@ import pytest
 
 from conftest import assert_floats_match_reference, golden_names, ulp_diff
 from oracle.oracle import OracleEnv, live_mask
+from oracle.ring_states import random_state  # noqa: F401  (its home; re-exported for the modules that import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -219,34 +220,6 @@ def test_teacher_forced_vs_golden(name, golden_cache):
 
 
 # ------------------------------------------------------------------------------------------------
-def random_state(rng, E, R, C, length, crowd=0.5, beyond=0.15, sorted_x=True):
-    """Random ring states incl. wrapped rings, empty and full roads, cars past the road end."""
-    x = np.zeros((E, R, C), np.float32)
-    v = np.zeros((E, R, C), np.float32)
-    w = np.zeros((E, R, C), np.float32)
-    leading = rng.randint(1, C, size=(E, R)).astype(np.int32)
-    n = np.minimum(rng.binomial(C - 2, crowd, size=(E, R)), C - 2)
-    n[rng.rand(E, R) < 0.1] = 0
-    n[rng.rand(E, R) < 0.1] = C - 2
-    lastcar = leading.copy()
-    for k in range(E):
-        for e in range(R):
-            cnt = int(n[k, e])
-            pos = np.sort(rng.uniform(-20, length * (1 + beyond), size=cnt))[::-1] if sorted_x \
-                else rng.uniform(-20, length * (1 + beyond), size=cnt)
-            s = int(leading[k, e])
-            for j in range(cnt):
-                s = s + 1 if s + 1 < C else 1
-                x[k, e, s] = pos[j]
-                v[k, e, s] = rng.choice([0.0, rng.uniform(0, 15)])
-                w[k, e, s] = rng.randint(0, 50)
-            lastcar[k, e] = s
-            # exit roads keep the +inf leader they got at reset (traffic_env.py:263; update_lights
-            # never touches them); train roads get theirs rewritten every tick
-            x[k, e, leading[k, e]] = np.inf
-    return x, v, w, leading, lastcar
-
-
 def load_both(eng, orc, x, v, w, leading, lastcar, phase, elapsed):
     eng.load_state(x, v, leading, lastcar, w=w)
     r, I = eng.r, eng.I
