@@ -729,6 +729,77 @@ typedef struct tfx_trip_stat_buffers {
 } tfx_trip_stat_buffers;
 int tfx_trip_stats(tfx_handle h, const int32_t *edges, int32_t n_bins, int32_t *cursor, const tfx_trip_stat_buffers *out,
                    int32_t flags, void *stream);
+/* Car-following measures on the device: what relates a car to its leader - net gaps, time headways, closing speeds with
+ * time to collision (TTC) and the deceleration rate to avoid a crash (DRAC), platoon joins, overlaps - as eleven words per
+ * road, from one read-only pass over the live cars (k_follow, csrc/tfx_follow.hpp).  The surrogate safety figures of a
+ * signal policy, platoon counts per approach, what a loop detector measures as headways, and a counter of followers the
+ * Jacobi IDM update pushed past their leader's rear bumper.  The reference has no counterpart; without this call the
+ * route is tfx_export_ring of every ring slot and array code over the image.
+ *
+ * Definition, as a function of the image tfx_export_ring would produce at that moment (on a ring-layout handle: of xv
+ * itself), so it is defined in every state a handle can be in, as the measures are.  For road e of env k take its cars in
+ * order from the head, j = 0 .. n-1: car j sits in ring slot wrap(leading + 1 + j), n is the count tfx_cars_on_roads
+ * returns; the fake leader is not a car.  Car j >= 1 forms a PAIR with its leader, car j-1 (F: the follower j, L: the
+ * leader).  The head car forms none: its leader is the light or a car of the next road - a stop-line or cross-road pair
+ * is out of scope of this call.  All arithmetic is float32, every operation rounded once in the order written, never
+ * contracted, divisions correctly rounded:
+ *   in range    the follower's x >= x_from (x_from = -INFINITY: every car; a NaN x is out of range); n_cars tests the
+ *               head car the same way.  A leader out of range still leads.
+ *   g           (x_L - x_F) - l_L: the net gap in IDM's own expression order (traffic_env.py:55).  l_L is the LEADER's
+ *               length: car_l, or on heterogeneous handles the l of the table row in the leader's side word
+ *   dv          v_F - v_L: the closing speed
+ * Per road, every counter counting pairs in range only:
+ *   n_cars      cars in range (tfx_road_measures' n_cars for the same x_from)
+ *   n_pairs     pairs in range
+ *   n_joined    pairs with g <= platoon_gap: the platoons on the road are n_cars - n_joined
+ *   n_overlap   pairs with g < 0
+ *   gap_sum     s = 0.0f, then s = s + g pair by pair in ascending j
+ *   gap_min     m = +INFINITY, then m = g < m ? g : m (a NaN g is never taken)
+ *   n_hw        pairs with v_F >= v_min
+ *   hw_sum      s = 0.0f, then s = s + g / v_F over those pairs in ascending j: the sum of the time headways
+ *   n_conflict  pairs with dv > 0 && g > 0 && g / dv < ttc_crit
+ *   ttc_min     m = +INFINITY, then m = t < m ? t : m over t = g / dv of the pairs with dv > 0 && g > 0
+ *   drac_max    m = 0.0f, then m = a > m ? a : m over a = (dv * dv) / (g + g) of the same pairs
+ * Minima and maxima are comparisons and selects, so a NaN is never taken.  A road without such pairs gets 0 / +INFINITY /
+ * 0 as its sums / minima / maximum.
+ *
+ * Outputs are device pointers, [E][R] by the reference's road id; any may be NULL, at least one must not be.  Without
+ * TFX_FOLLOW_ACCUMULATE every bound output is overwritten.  With it: integers add; each float sum takes ONE float32 add
+ * of the road's value (out = out + value); gap_min and ttc_min become value < out ? value : out; drac_max becomes value >
+ * out ? value : out.  The caller initialises an accumulating buffer: 0 for the counters, the sums and drac_max, +INFINITY
+ * for gap_min and ttc_min.
+ *
+ * One launch on `stream`, no host synchronisation; nothing in the handle or in the caller's bound state is written:
+ * captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the launch.  TFX_MEASURE_GRID and
+ * TFX_GRID_CAP cap the launch as they cap the measures'.  TFX_EINVAL: a NULL handle, a NULL `p` or `out`, all eleven
+ * pointers NULL, unknown flag bits, a NaN in any field of `p` (infinities are fine), v_min <= 0 (the headway is never a
+ * division by zero); TFX_ESTATE before tfx_bind_buffers.  A refused call launches nothing.  gym_traffic/devrng.py
+ * road_following states the definition in NumPy. */
+typedef struct tfx_follow_params {
+  float x_from;        /* followers (and, for n_cars, cars) with x >= x_from are in range */
+  float platoon_gap;   /* g <= platoon_gap: the follower belongs to its leader's platoon */
+  float v_min;         /* > 0: slower followers have no time headway */
+  float ttc_crit;      /* g / dv < ttc_crit: a conflict */
+} tfx_follow_params;
+typedef struct tfx_follow_buffers {
+  int32_t *n_cars;     /* [E][R] by road id; any may be NULL */
+  int32_t *n_pairs;
+  int32_t *n_joined;
+  int32_t *n_overlap;
+  float *gap_sum;
+  float *gap_min;
+  int32_t *n_hw;
+  float *hw_sum;
+  int32_t *n_conflict;
+  float *ttc_min;
+  float *drac_max;
+} tfx_follow_buffers;
+enum { TFX_FOLLOW_ACCUMULATE = 1 };
+int tfx_road_following(tfx_handle h, const tfx_follow_params *p, const tfx_follow_buffers *out, int32_t flags,
+                       void *stream);
+/* Test support: the launch geometry tfx_road_following uses for this handle - workgroups, and wavefronts (one per
+ * (env, tile) item at a time), like tfx_measure_launch. */
+int tfx_follow_launch(tfx_handle h, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

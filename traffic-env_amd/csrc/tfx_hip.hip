@@ -21,6 +21,7 @@
 #include <new>
 
 #include "tfx_cells.hpp"
+#include "tfx_follow.hpp"
 #include "tfx_frames.hpp"
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
@@ -1181,6 +1182,40 @@ int tfx_road_measures(tfx_handle h, float halt_speed, float x_from, const tfx_me
 }
 
 int tfx_measure_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  return report_launch(tile_grid(h, true), grid, waves);
+}
+
+int tfx_road_following(tfx_handle h, const tfx_follow_params *p, const tfx_follow_buffers *out, int32_t flags,
+                       void *stream) {
+  if (!p) return fail(TFX_EINVAL, "following: p is null");
+  if (!out) return fail(TFX_EINVAL, "following: out is null");
+  if (int rc = check_handle(h, false)) return rc;
+  if (!out->n_cars && !out->n_pairs && !out->n_joined && !out->n_overlap && !out->gap_sum && !out->gap_min && !out->n_hw &&
+      !out->hw_sum && !out->n_conflict && !out->ttc_min && !out->drac_max)
+    return fail(TFX_EINVAL, "following: every output pointer is null");
+  if (flags & ~TFX_FOLLOW_ACCUMULATE) return fail(TFX_EINVAL, "unknown following flags 0x%x", flags);
+  if (std::isnan(p->x_from) || std::isnan(p->platoon_gap) || std::isnan(p->v_min) || std::isnan(p->ttc_crit))
+    return fail(TFX_EINVAL, "following: x_from / platoon_gap / v_min / ttc_crit is NaN");
+  if (!(p->v_min > 0.0f)) return fail(TFX_EINVAL, "following: v_min %g is not above 0", (double)p->v_min);
+  if (int rc = check_handle(h, true)) return rc;
+  FollowOut o{};
+  o.n_cars = out->n_cars;
+  o.n_pairs = out->n_pairs;
+  o.n_joined = out->n_joined;
+  o.n_overlap = out->n_overlap;
+  o.gap_sum = out->gap_sum;
+  o.gap_min = out->gap_min;
+  o.n_hw = out->n_hw;
+  o.hw_sum = out->hw_sum;
+  o.n_conflict = out->n_conflict;
+  o.ttc_min = out->ttc_min;
+  o.drac_max = out->drac_max;
+  o.accumulate = (flags & TFX_FOLLOW_ACCUMULATE) ? 1 : 0;
+  return launch_query(k_follow, tile_grid(h, true), stream, h->d, *p, o);
+}
+
+int tfx_follow_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
   return report_launch(tile_grid(h, true), grid, waves);
 }

@@ -1,5 +1,5 @@
 // tfx_walk.hpp - the one walk of the live cars that the read-only road kernels share: k_measure (tfx_measure.hpp),
-// k_cells (tfx_cells.hpp), k_ages (tfx_travel.hpp) and k_frames (tfx_frames.hpp).  Device only.
+// k_cells (tfx_cells.hpp), k_ages (tfx_travel.hpp), k_frames (tfx_frames.hpp) and k_follow (tfx_follow.hpp).  Device only.
 //
 // The kernels take one wavefront per (env or frame, tile) item, four to a workgroup, striding over the items, lane per
 // road as in k_move_t (tfx_move_t.hpp):
@@ -16,7 +16,9 @@
 //   * walk_cars, ring layout (tfx_config.layout = 0, the non-default one): each lane walks the ring slots of its road
 //     from leading + 1 with wrap1.
 //   * Either way `visit` sees a road's cars from the head to the tail: float32 sums taken in that order are
-//     reproducible bit for bit and equal on both layouts.
+//     reproducible bit for bit and equal on both layouts.  The car visited just before a car is its leader: k_follow
+//     carries that car's (x, v, l) from one visit to the next, in state of its own that lives outside the walk - the
+//     walk keeps nothing between visits, neither across its blocks of WALK_P rows nor over the rows it skips.
 #pragma once
 #include "tfx_common.hpp"
 #include "tfx_move_t.hpp"
@@ -72,7 +74,8 @@ __device__ __forceinline__ void walk_cars(const Dev &d, const TileRoad &r, int l
   // A word is zeroed ahead of the loads where visit can see it unloaded: every word in the uniform form (lanes without a
   // car) and with XV == 1 (the half pair, and the side word where side_wanted is false); a plane never asked for
   // otherwise.  Words that every visited car loads are not: the zero would only wait for the loads of the round before
-  // (profiles/r06_query_walk.txt has the figures).
+  // (profiles/r06_query_walk.txt has the figures).  A side plane the template takes but side_wanted declines (k_follow on
+  // a single-archetype handle) is zeroed as well.
   constexpr bool ZERO_XV = UNIFORM || XV != 2, ZERO_SIDE = UNIFORM || XV == 1 || !SIDE;
   if (d.layout == 1) {
     const int hb = r.live ? d.hb[r.id] : 0;  // rows a two-tick pass left empty at the top of the column
@@ -87,7 +90,7 @@ __device__ __forceinline__ void walk_cars(const Dev &d, const TileRoad &r, int l
 #pragma unroll
       for (int u = 0; u < WALK_P; ++u) {
         if (ZERO_XV) c[u] = f2v{0.0f, 0.0f};
-        if (ZERO_SIDE) sw[u] = 0.0f;
+        if (ZERO_SIDE || !side) sw[u] = 0.0f;
         if (k0 + u >= hb && k0 + u < rows) {
           if (XV == 2) c[u] = reinterpret_cast<const f2v *>(col)[(size_t)(k0 + u) * 64];
           if (XV == 1) c[u].x = col[(size_t)(k0 + u) * 64].x;

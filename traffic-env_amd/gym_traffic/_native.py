@@ -17,6 +17,7 @@ MAX_CELLS = 32                          # TFX_MAX_CELLS
 TRAVEL_ACCUMULATE = 1                   # flag of tfx_car_ages and tfx_trip_stats
 MAX_TRIP_BINS = 32                      # the most bins tfx_trip_stats takes
 FRAMES_ROADS_ONLY = 1                   # flag of tfx_frames
+FOLLOW_ACCUMULATE = 1                   # flag of tfx_road_following
 FRAME_PX_MIN, FRAME_PX_MAX = 8, 256     # TFX_FRAME_PX_MIN, TFX_FRAME_PX_MAX
 DEMAND_MAX_PROFILES, DEMAND_MAX_SEGMENTS, DEMAND_MAX_CDF = 16, 64, 256   # limits of tfx_set_demand
 
@@ -61,6 +62,16 @@ class TfxAgeBuffers(C.Structure):
 class TfxTripStatBuffers(C.Structure):
     _fields_ = [("count", C.c_void_p), ("tick_sum", C.c_void_p), ("tick_max", C.c_void_p), ("lost", C.c_void_p),
                 ("hist", C.c_void_p)]
+
+
+class TfxFollowParams(C.Structure):
+    _fields_ = [("x_from", C.c_float), ("platoon_gap", C.c_float), ("v_min", C.c_float), ("ttc_crit", C.c_float)]
+
+
+class TfxFollowBuffers(C.Structure):
+    _fields_ = [("n_cars", C.c_void_p), ("n_pairs", C.c_void_p), ("n_joined", C.c_void_p), ("n_overlap", C.c_void_p),
+                ("gap_sum", C.c_void_p), ("gap_min", C.c_void_p), ("n_hw", C.c_void_p), ("hw_sum", C.c_void_p),
+                ("n_conflict", C.c_void_p), ("ttc_min", C.c_void_p), ("drac_max", C.c_void_p)]
 
 
 class TfxDemand(C.Structure):
@@ -143,6 +154,9 @@ _PROTOS = {
     "tfx_frame_size": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tfx_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "tfx_frames_launch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_road_following": (C.c_int, [C.c_void_p, C.POINTER(TfxFollowParams), C.POINTER(TfxFollowBuffers), C.c_int32,
+                                     C.c_void_p]),
+    "tfx_follow_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

@@ -37,6 +37,10 @@ RoadCells = collections.namedtuple("RoadCells", "n_cars speed_sum")
 CarAges = collections.namedtuple("CarAges", "n_cars age_sum age_max")
 # what trip_stats() returns: [E] device tensors, hist [E, n_bins] or None (tfx_trip_stats, include/tfx.h)
 TripStats = collections.namedtuple("TripStats", "count tick_sum tick_max lost hist")
+# what road_following() returns: eleven [E, R] device tensors by road id (tfx_road_following, include/tfx.h)
+RoadFollowing = collections.namedtuple("RoadFollowing", "n_cars n_pairs n_joined n_overlap gap_sum gap_min n_hw hw_sum "
+                                                        "n_conflict ttc_min drac_max")
+_FOLLOW_FLOATS = ("gap_sum", "gap_min", "hw_sum", "ttc_min", "drac_max")
 
 
 def _ptr(t):
@@ -208,6 +212,7 @@ class TfxEngine(object):
         self._cars = torch.zeros((E, R), dtype=torch.int32, device=dev)
         self._measures = None       # road_measures(): made on first use
         self._ages = None           # car_ages(): made on first use
+        self._following = None      # road_following(): made on first use
         self._trips = {}            # trip_stats(): made on first use, per number of bins
         self._cells = {}            # road_cells(): made on first use, per number of cells
         self._frames = {}           # frames(): made on first use, per (frames, px); holds the background after that
@@ -451,6 +456,46 @@ class TfxEngine(object):
         """(workgroups, wavefronts) of the road_measures launch of this engine (tfx_measure_launch; tests)."""
         g, w = C.c_int32(), C.c_int32()
         nat.check(self.lib.tfx_measure_launch(self.h, C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def road_following(self, platoon_gap, v_min, ttc_crit, x_from=None, out=None, accumulate=False):
+        """The car-following measures per road, from one read-only launch over the live cars (tfx_road_following,
+        include/tfx.h; gym_traffic.devrng.road_following states the definition in NumPy): -> RoadFollowing, eleven [E, R]
+        device tensors by road id - int32 counters, float32 gap_sum, gap_min, hw_sum, ttc_min, drac_max.  Car j >= 1 of
+        a road pairs with its leader j-1; with g = (x_L - x_F) - l_L and dv = v_F - v_L, over the pairs whose follower has
+        x >= x_from (None: every car): n_pairs; n_joined (g <= platoon_gap: platoons = n_cars - n_joined); n_overlap
+        (g < 0); gap_sum, gap_min; n_hw, hw_sum (g / v_F where v_F >= v_min > 0); n_conflict (dv > 0, g > 0 and g / dv <
+        ttc_crit), ttc_min and drac_max ((dv * dv) / (g + g)) over the closing pairs; n_cars: the cars in range.
+        accumulate: counters and sums are added to, minima and the maximum combined with what is there, instead of
+        overwritten.  out: the caller's RoadFollowing (any member None: not computed; for accumulate the caller starts
+        gap_min / ttc_min at +inf and the rest at 0); default: tensors the engine allocates once - zeros, gap_min and
+        ttc_min +inf - and reuses.  No host synchronisation; nothing of the env state is written."""
+        want = {f: torch.float32 if f in _FOLLOW_FLOATS else torch.int32 for f in RoadFollowing._fields}
+        if out is None:
+            if self._following is None:
+                self._following = RoadFollowing(*[
+                    torch.full((self.E, self.R), float("inf") if f in ("gap_min", "ttc_min") else 0, dtype=want[f],
+                               device=self.device) for f in RoadFollowing._fields])
+            out = self._following
+        else:
+            out = RoadFollowing(*out)
+            for name, t in zip(RoadFollowing._fields, out):
+                if t is not None and (t.dtype != want[name] or tuple(t.shape) != (self.E, self.R) or not t.is_contiguous()
+                                      or not t.is_cuda):
+                    raise ValueError("road_following(out=): %s must be a contiguous %s [%d, %d] device tensor"
+                                     % (name, want[name], self.E, self.R))
+        p = nat.TfxFollowParams(float("-inf") if x_from is None else float(x_from), float(platoon_gap), float(v_min),
+                                float(ttc_crit))
+        b = nat.TfxFollowBuffers(*[_ptr(t) for t in out])
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_road_following(self.h, C.byref(p), C.byref(b),
+                                                  nat.FOLLOW_ACCUMULATE if accumulate else 0, self._stream()))
+        return out
+
+    def follow_launch(self):
+        """(workgroups, wavefronts) of the road_following launch of this engine (tfx_follow_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_follow_launch(self.h, C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
 
     def car_ages(self, accumulate=False, out=None):

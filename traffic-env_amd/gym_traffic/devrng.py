@@ -18,7 +18,8 @@ envs an in-place tfx_clone_envs applies, and what tfx_road_measures computes per
 tfx_road_cells (cars and speeds per cell of road); `cell_edges` makes the uniform edges that leave no car out.  `frames`
 states what tfx_frames draws (top-view RGBA pictures of chosen envs), `frame_geometry` where every road lies in them.
 `car_ages` and `trip_stats` state the travel-time rules (tfx_car_ages, tfx_trip_stats): the ages of the live cars per
-road, and the finished trips of every env's log reduced from a cursor on.
+road, and the finished trips of every env's log reduced from a cursor on.  `road_following` states the car-following
+measures (tfx_road_following): gaps, headways, time to collision and platoon joins of every car and its leader.
 
 `demand_tables`, `demand_segment` and `demand_counts` belong to the demand profiles (tfx_set_demand, rule 4 of
 include/tfx.h): the threshold tables the device reads, the segment of a clock tick, and the rule itself in NumPy - a pure
@@ -167,6 +168,76 @@ def road_measures(x, v, leading, lastcar, C, halt_speed=0.1, x_from=None):
         queue += unbroken & live
         total = np.where(inr, added, total)
     return cars.reshape(shape), halted.reshape(shape), queue.reshape(shape), total.reshape(shape)
+
+
+FOLLOW_FIELDS = ("n_cars", "n_pairs", "n_joined", "n_overlap", "gap_sum", "gap_min", "n_hw", "hw_sum", "n_conflict",
+                 "ttc_min", "drac_max")
+
+
+def road_following(x, v, leading, lastcar, C, params, car_l=4.0, arch_rows=None, arch_l=None):
+    """The definition of tfx_road_following (include/tfx.h) in NumPy, over ring planes: x, v float32 [..., R, C] by ring
+    slot (what tfx_export_ring produces), leading / lastcar int [..., R]; params = (x_from or None, platoon_gap, v_min,
+    ttc_crit).  A car's length: car_l, or - with arch_rows uint8 [..., R, C] (the archetype row of every ring slot) and
+    arch_l float32 [rows of the table] - arch_l[arch_rows].  -> a tuple in the order of FOLLOW_FIELDS, [..., R]: int32
+    counters, float32 gap_sum, gap_min, hw_sum, ttc_min, drac_max.  Car j of a road (j = 0: the head) sits in slot
+    wrap(leading + 1 + j); car j >= 1 is the follower F of a pair whose leader L is car j-1; the pair is in range iff
+    x_F >= x_from.  g = (x_L - x_F) - l_L, dv = v_F - v_L; every operation one float32 rounding, sums in ascending j
+    from 0, minima from +inf and the maximum from 0 by compare and select - the order and the NaN behaviour the device
+    keeps, so the bits agree."""
+    C = int(C)
+    x_from, platoon_gap, v_min, ttc_crit = params
+    lo = np.float32(-np.inf if x_from is None else x_from)
+    join, slow, crit = np.float32(platoon_gap), np.float32(v_min), np.float32(ttc_crit)
+    if np.isnan([lo, join, slow, crit]).any() or not slow > 0:
+        raise ValueError("road_following: a NaN parameter, or v_min is not above 0")
+    x = np.asarray(x, np.float32)
+    v = np.asarray(v, np.float32)
+    shape = x.shape[:-1]
+    x, v = x.reshape(-1, C), v.reshape(-1, C)
+    ld = np.asarray(leading, np.int64).reshape(-1)
+    lc = np.asarray(lastcar, np.int64).reshape(-1)
+    n = lc - ld + np.where(ld > lc, C - 1, 0)
+    N = len(ld)
+    rows = np.arange(N)
+    if arch_rows is not None:
+        lengths = np.asarray(arch_l, np.float32)[np.asarray(arch_rows).reshape(-1, C)]
+    zero = np.float32(0)
+    cars, pairs, joined, overlap, hw, conflict = [np.zeros(N, np.int32) for _ in range(6)]
+    gap_sum, hw_sum, drac_max = [np.zeros(N, np.float32) for _ in range(3)]
+    gap_min, ttc_min = [np.full(N, np.inf, np.float32) for _ in range(2)]
+    xl, vl, ll = [np.zeros(N, np.float32) for _ in range(3)]      # the leader: the car taken just before
+    have = np.zeros(N, bool)
+    for j in range(C - 1):
+        live = j < n
+        slot = ld + 1 + j
+        slot = np.where(slot > C - 1, slot - (C - 1), slot)
+        slot = np.where(live, slot, 0)
+        xj, vj = x[rows, slot], v[rows, slot]
+        lj = np.full(N, car_l, np.float32) if arch_rows is None else lengths[rows, slot]
+        with np.errstate(all="ignore"):
+            inr = live & (xj >= lo)
+            pair = inr & have
+            g = ((xl - xj).astype(np.float32) - ll).astype(np.float32)
+            dv = (vj - vl).astype(np.float32)
+            timed = pair & (vj >= slow)
+            closing = pair & (dv > zero) & (g > zero)
+            ttc = (g / dv).astype(np.float32)
+            drac = ((dv * dv).astype(np.float32) / (g + g).astype(np.float32)).astype(np.float32)
+            cars += inr
+            pairs += pair
+            joined += pair & (g <= join)
+            overlap += pair & (g < zero)
+            gap_sum = np.where(pair, (gap_sum + g).astype(np.float32), gap_sum)
+            gap_min = np.where(pair & (g < gap_min), g, gap_min)
+            hw += timed
+            hw_sum = np.where(timed, (hw_sum + (g / vj).astype(np.float32)).astype(np.float32), hw_sum)
+            conflict += closing & (ttc < crit)
+            ttc_min = np.where(closing & (ttc < ttc_min), ttc, ttc_min)
+            drac_max = np.where(closing & (drac > drac_max), drac, drac_max)
+        xl, vl, ll = np.where(live, xj, xl), np.where(live, vj, vl), np.where(live, lj, ll)
+        have = have | live
+    out = (cars, pairs, joined, overlap, gap_sum, gap_min, hw, hw_sum, conflict, ttc_min, drac_max)
+    return tuple(a.reshape(shape) for a in out)
 
 
 def car_ages(w, leading, lastcar, C, now, het=False):

@@ -55,6 +55,10 @@ from gym_traffic.spawner import ArrivalStreams
 
 # what TrafficVecEnv.measures() returns: the engine's four per-road tensors and the views derived from them
 VecMeasures = collections.namedtuple("VecMeasures", "n_cars n_halted queue speed_sum halted cars mean_speed pressure")
+# what TrafficVecEnv.following() returns: the engine's eleven per-road tensors and the views derived from them
+VecFollowing = collections.namedtuple("VecFollowing", "n_cars n_pairs n_joined n_overlap gap_sum gap_min n_hw hw_sum n_conflict "
+                                                      "ttc_min drac_max pairs mean_gap min_gap platoons mean_platoon_size "
+                                                      "mean_headway_s min_ttc_s conflicts max_drac overlaps")
 # what TrafficVecEnv.cell_obs() returns: the engine's two per-cell tensors and the image a convolutional policy reads
 VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
 # what TrafficVecEnv.travel_times() returns: per-env travel-time figures, finished trips and cars still on the map
@@ -485,6 +489,46 @@ class TrafficVecEnv(object):
         pressure.index_add_(1, cell, n[:, :r] - n[:, nxt])
         return VecMeasures(rm.n_cars, rm.n_halted, rm.queue, rm.speed_sum, halted, cars, mean_speed,
                            pressure.view(eng.E, eng.I, 2))
+
+    def following(self, platoon_gap=10.0, v_min=0.5, ttc_crit=3.0, x_from=None, accumulate=False):
+        """The car-following measures of every env, on the device, with no host synchronisation: one read-only launch
+        over the live cars (TfxEngine.road_following / tfx_road_following, include/tfx.h) plus a few torch expressions
+        over its eleven words per road.  A car pairs with the car ahead of it on its road; g is the net gap to that
+        leader's rear bumper, dv the closing speed.  -> VecFollowing:
+            n_cars .. drac_max  the engine's RoadFollowing tensors [E, R] per road id, overwritten by the next call - or,
+                        accumulate=True, combined with it (measure once per decision: conflicts per car-decision)
+        and over the train roads:
+            pairs       int64 [E] - pairs whose follower has x >= x_from (None: all)
+            mean_gap    float64 [E] - sum of gap_sum / pairs, in metres; nan without pairs
+            min_gap     float32 [E] - the smallest g; +inf without pairs
+            platoons    int64 [E, R] - n_cars - n_joined per road (every road): the groups of cars no further than
+                        platoon_gap apart; mean_platoon_size float64 [E] - cars / platoons, nan without cars
+            mean_headway_s float64 [E] - sum of hw_sum / sum of n_hw: mean of g / v_F over the followers with v_F >= v_min;
+                        nan without such pairs
+            min_ttc_s   float32 [E] - the smallest g / dv over the closing pairs (dv > 0, g > 0); +inf without
+            conflicts   int64 [E] - closing pairs with g / dv < ttc_crit
+            max_drac    float32 [E] - the largest dv^2 / 2g over the closing pairs, 0 without
+            overlaps    int64 [E] - pairs with g < 0: followers past their leader's rear bumper
+        With accumulate=True the derived views are those of the accumulated tensors."""
+        eng = self.engine
+        rf = eng.road_following(platoon_gap, v_min, ttc_crit, x_from=x_from, accumulate=accumulate)
+        r = eng.r
+        nan = torch.full((eng.E,), float("nan"), dtype=torch.float64, device=eng.device)
+
+        def total(t):
+            return t[:, :r].sum(dim=1, dtype=torch.int64)
+
+        def ratio(num, den):
+            return torch.where(den > 0, num / den.clamp(min=1), nan)
+        pairs = total(rf.n_pairs)
+        platoons = rf.n_cars.long() - rf.n_joined.long()
+        return VecFollowing(*rf, pairs,
+                            ratio(rf.gap_sum[:, :r].sum(dim=1, dtype=torch.float64), pairs),
+                            rf.gap_min[:, :r].min(dim=1).values,
+                            platoons, ratio(total(rf.n_cars).double(), platoons[:, :r].sum(dim=1)),
+                            ratio(rf.hw_sum[:, :r].sum(dim=1, dtype=torch.float64), total(rf.n_hw)),
+                            rf.ttc_min[:, :r].min(dim=1).values, total(rf.n_conflict),
+                            rf.drac_max[:, :r].max(dim=1).values, total(rf.n_overlap))
 
     def cell_obs(self, n_cells=8, edges=None, v_scale=None, accumulate=False):
         """The discrete traffic state encoding of every env, on the device, with no host synchronisation: every approach
