@@ -21,12 +21,14 @@
 // ~65 vector instructions against ~110 per (up to 64-car) road for the lane-per-car kernels, and
 // the bytes moved are the live ones.  Ring indices (leading/lastcar), counters and every float are
 // bit-identical to the ring-layout kernels; tfx_export_ring / tfx_import_ring convert.
+// What this walk has in common with the other tile walkers (k_move_ts, the two-tick passes and their edge work) - the
+// lane's road and columns, the IDM step under the domain test, the counts, the arrivals of heterogeneous cars, the
+// road's outputs, the kernel's epilogue - is tfx_tile.hpp's.
 #pragma once
 #include "tfx_common.hpp"
+#include "tfx_tile.hpp"
 
 namespace tfx {
-
-typedef float f2v __attribute__((ext_vector_type(2)));
 
 // index of position 0 of road e of env in a transposed array (T or the outbox); position k is 64 k
 // pairs further
@@ -59,34 +61,25 @@ __global__ __launch_bounds__(256) void k_move_t(const Dev d, const int tidx) {
   const int C = d.C;
   const long tiles = (long)d.E * d.G;
   const long nw = (long)gridDim.x * 4;
-  const int tick_sp = (d.spawn_mode == TFX_SPAWN_PERIODIC) ? tick % d.spawn_period : 0;
+  const int tick_sp = spawn_phase(d, tick);
 
   unsigned long long my_updates = 0;
 
   for (long tile = (long)blockIdx.x * 4 + wv; tile < tiles; tile += nw) {
     const int env = (int)(tile / d.G);  // a tile never straddles envs
-    const int e_slot = d.slot_road[(int)(tile - (long)env * d.G) * 64 + lane];
-    const bool valid = e_slot >= 0;
-    const int e = valid ? e_slot : 0;
-    const int id = env * d.R + e;
-    const bool run = valid && !env_frozen(d, env, tick);
+    TileLane tl;
+    tl.road(d, tile, env, lane);
+    const int e = tl.e, id = tl.id;
+    const bool run = tl.valid && !env_frozen(d, env, tick);
     const RoadPrep p = prep_road(d, id, env, e, tick, tick_sp, tidx, run, run);
     const int n_old = run ? p.n_old : 0;
     const int n_sp = run ? p.n_tot - p.n_old : 0;
 
-    float2 *col = d.xv + ((size_t)tile * d.trows) * 64 + lane;     // T[k] of this road = col[k * 64]
-    float2 *ocol = d.outb + ((size_t)tile * KP) * 64 + lane;       // outbox column of this road (KP rows)
-    float *wcol = W ? d.w + ((size_t)tile * d.trows) * 64 + lane : nullptr;
-    float *owcol = W ? d.outw + ((size_t)tile * KP) * 64 + lane : nullptr;
+    tl.columns<W>(d, tile, lane);
+    float2 *const col = tl.col, *const ocol = tl.ocol;
+    float *const wcol = tl.wcol, *const owcol = tl.owcol;
 
-    // longest road of the tile (wave-uniform loop bound)
-    int kmax = n_old;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o = __shfl_xor(kmax, off, 64);
-      kmax = o > kmax ? o : kmax;
-    }
-    kmax = __builtin_amdgcn_readfirstlane(kmax);
+    const int kmax = wave_max(n_old);  // longest road of the tile (wave-uniform loop bound)
 
     // per-road running state
     float xprev = p.xL, vprev = 0.0f, llv = 0.0f;  // leader of the next car: starts as the fake one
@@ -96,29 +89,13 @@ __global__ __launch_bounds__(256) void k_move_t(const Dev d, const int tidx) {
                                      //   the road popped more than TFX_KP cars and stays uncompacted
     float tail_x = 0.0f;
     int last_a = 0;  // HET: table row of the last car processed (the road's tail after the move)
-    // wrapped ring: x, not v, is tested on slots 1..lastcar (:210) = the cars from index kq on
-    const int kq = (p.ld > p.lc) ? C - 1 - p.ld : 0x7fffffff;
+    const int kq = kq_of(p, C);
 
     // One car of this lane's road.  Runs under `if (active)`: the EXEC mask keeps the running state
     // of lanes whose road is shorter than the tile's longest untouched.
     // NT bit 0: non-temporal loads, bit 1: non-temporal stores (every byte is touched once per tick)
-    auto ld2 = [&](const float2 *ptr) {
-      if (NT & 1) {
-        const f2v t = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(ptr));
-        return make_float2(t.x, t.y);
-      }
-      return *ptr;
-    };
-    auto st2 = [&](float2 *ptr, float a, float b) {
-      if (NT & 2) {
-        f2v t;
-        t.x = a;
-        t.y = b;
-        __builtin_nontemporal_store(t, reinterpret_cast<f2v *>(ptr));
-      } else {
-        *ptr = make_float2(a, b);
-      }
-    };
+    auto ld2 = [&](const float2 *ptr) { return ld_nt<(NT & 1) != 0>(ptr); };
+    auto st2 = [&](float2 *ptr, float a, float b) { st_nt<(NT & 2) != 0>(ptr, a, b); };
     auto step = [&](int k, float x, float v, float wv) {
       float xn, vn;
       if (HET) {
@@ -127,9 +104,7 @@ __global__ __launch_bounds__(256) void k_move_t(const Dev d, const int tidx) {
         idm_step_het(d, me, x, v, xprev, vprev, llv, xn, vn);
         llv = me[AR_L];
       } else {
-        const bool off_domain = __builtin_amdgcn_ballot_w64(!idm_fast_domain(v)) != 0ull;
-        if (d.fastdiv && !off_domain) idm_step_fast(d, x, v, xprev, vprev, llv, xn, vn);
-        else idm_step(d, x, v, xprev, vprev, llv, xn, vn);
+        idm_plain(d, x, v, xprev, vprev, llv, xn, vn);
         llv = d.car_l;
       }
       xprev = x;  // OLD state leads the next car (Jacobi)
@@ -152,9 +127,7 @@ __global__ __launch_bounds__(256) void k_move_t(const Dev d, const int tidx) {
         if (W) wcol[(size_t)(k - shift) * 64] = wv;
       }
       kpop += pop ? 1 : 0;
-      const float wq = (k >= kq) ? xn : vn;
-      n_wait += (wq < d.thresh) ? 1 : 0;
-      n_det += (xn > d.near_end) ? 1 : 0;
+      count_car(d, k, kq, xn, vn, n_wait, n_det);
       tail_x = xn;
     };
 
@@ -185,34 +158,9 @@ __global__ __launch_bounds__(256) void k_move_t(const Dev d, const int tidx) {
     }
     // ---- cars spawned this tick (add_car :97-114): they queue behind the tail ------------------
     if (__builtin_amdgcn_ballot_w64(n_sp > 0) != 0ull) {
-      int smax = n_sp;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(smax, off, 64);
-        smax = o > smax ? o : smax;
-      }
-      smax = __builtin_amdgcn_readfirstlane(smax);
+      const int smax = wave_max(n_sp);
       if (HET) {
-        // add_car :97-114 car by car: each queues behind the road's tail at the moment it is created - the tail's
-        // OWN length and minimum gap - and brings the row add_new_cars drew for it (:164)
-        int lc = ring_adv(p.ld, n_old, C);
-        float tx = d.tailx[id];
-        int ta = d.taila[id];
-        const int ej = d.entry_idx[e];
-        const uint8_t *rows = (d.spawn_arch && d.spawn_mode == TFX_SPAWN_COUNTS && ej >= 0)
-                                  ? d.spawn_arch + (size_t)tidx * d.spawn_arch_stride +
-                                        ((size_t)env * d.n_entry + ej) * d.spawn_arch_S
-                                  : nullptr;
-        for (int s = 0; s < smax; ++s)
-          if (s < n_sp) {
-            const int row = (rows && s < d.spawn_arch_S) ? (rows[s] & (TFX_MAX_ARCH - 1)) : 0;
-            const float start = (lc != p.ld) ? (tx - s_arch[ta * ARCH_W + AR_L]) - s_arch[ta * ARCH_W + AR_S0] : INFINITY;
-            const float xs = (start < 0.0f) ? start : 0.0f;
-            step(n_old + s, xs, s_arch[row * ARCH_W + AR_V], side_pack(tick, row));
-            lc = wrap1(lc + 1, C);
-            tx = xs;
-            ta = row;
-          }
+        het_spawns(d, p, id, env, e, tick, tidx, n_old, n_sp, smax, s_arch, step);
       } else {
         for (int s = 0; s < smax; ++s)
           if (s < n_sp) step(n_old + s, spawned_x(d, p.xs0, s), d.car_v, (float)tick);  // w = spawn tick
@@ -222,26 +170,13 @@ __global__ __launch_bounds__(256) void k_move_t(const Dev d, const int tidx) {
     // ---- phase W -------------------------------------------------------------------------------
     if (run) {
       const int n_tot = p.n_tot;
-      if (e < d.r) {
-        int *ob = d.obs + (size_t)env * d.obs_len;
-        if (n_tot > 0) {
-          d.waiting[(size_t)env * d.r + e] += n_wait;
-          ob[d.r + e] = n_det;
-        }
-        ob[e] = (d.agent_mode && tidx > 0) ? ob[e] + kpop : kpop;
-        if (kpop > 0) d.passed_dst[(size_t)env * d.I + e % d.I] = 1;
-      }
-      d.rec[id] = make_int4(rec_pack(kpop, p.ld, C), rec_y(p.ovf_sp, kpop > KP), __float_as_int(tail_x),
-                            n_tot | (HET ? last_a << 16 : 0));
-      if (far || kpop > KP) d.env_flag[env] = tick + 1;
-      d.leadx[id] = p.xL;
+      store_tick_outputs(d, p, env, e, id, tick, n_tot, n_wait, n_det, kpop, tail_x, HET ? last_a : 0, far || kpop > KP,
+                         d.agent_mode && tidx > 0);
       my_updates += (unsigned long long)n_tot;
     }
   }
 
-  for (int off = 32; off > 0; off >>= 1) my_updates += __shfl_down(my_updates, off);
-  if (lane == 0 && my_updates) veh_add(d.veh, my_updates);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *d.tickB = tick;
+  finish_walk(d, lane, my_updates, tick);
 }
 
 }  // namespace tfx

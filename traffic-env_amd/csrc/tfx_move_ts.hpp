@@ -13,7 +13,8 @@
 //      road with more than TFX_KP pops is written back uncompacted, every car in its own row),
 //   4. the per-road counts meet in LDS and segment 0 writes the road's outputs.
 // Same arithmetic, same stores: results are bit-identical to k_move_t (every transposed-layout test
-// runs through this kernel whenever the launch is small).
+// runs through this kernel whenever the launch is small).  The pieces it shares with the other tile walkers - the IDM
+// step, the counts, the columns, the road's outputs - are tfx_tile.hpp's.
 #pragma once
 #include "tfx_common.hpp"
 #include "tfx_move_t.hpp"
@@ -30,11 +31,12 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
   const int tick = *d.tickA;
   const int C = d.C;
   const long tiles = (long)d.E * d.G;
-  const int tick_sp = (d.spawn_mode == TFX_SPAWN_PERIODIC) ? tick % d.spawn_period : 0;
+  const int tick_sp = spawn_phase(d, tick);
   unsigned long long my_updates = 0;
 
   for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int env = (int)(tile / d.G);
+    // (the lane's road, written out: through TileLane::road the KS = 8, 32 and 64 forms take one register more or less)
     const int e_slot = d.slot_road[(int)(tile - (long)env * d.G) * 64 + lane];
     const bool valid = e_slot >= 0;
     const int e = valid ? e_slot : 0;
@@ -45,23 +47,17 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
     const RoadPrep p = prep_road(d, id, env, e, tick, tick_sp, tidx, run, false);
     const int n_old = run ? p.n_old : 0;
     const int n_tot = run ? p.n_tot : 0;
-    float2 *col = d.xv + ((size_t)tile * d.trows) * 64 + lane;
-    float2 *ocol = d.outb + ((size_t)tile * KP) * 64 + lane;
-    float *wcol = W ? d.w + ((size_t)tile * d.trows) * 64 + lane : nullptr;
-    float *owcol = W ? d.outw + ((size_t)tile * KP) * 64 + lane : nullptr;
+    TileLane tl;
+    tl.columns<W>(d, tile, lane);
+    float2 *const col = tl.col, *const ocol = tl.ocol;
+    float *const wcol = tl.wcol, *const owcol = tl.owcol;
     // rows the second tick of a pair left empty at the top of the column (tfx_move_tt.hpp: a handle that runs its calls
     // as pairs takes its single ticks here when the launch is small): read past them, write the column compacted
     const int hb = (run && d.hb) ? d.hb[id] : 0;
     const float2 *colr = col + (size_t)hb * 64;
     const float *wcolr = W ? wcol + (size_t)hb * 64 : nullptr;
 
-    int kmax = n_tot;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o = __shfl_xor(kmax, off, 64);
-      kmax = o > kmax ? o : kmax;
-    }
-    kmax = __builtin_amdgcn_readfirstlane(kmax);
+    const int kmax = wave_max(n_tot);
     const int kseg = (kmax + S - 1) / S;
     const int k0 = seg * kseg;
     const int k1 = (k0 + kseg < kmax) ? k0 + kseg : kmax;
@@ -70,11 +66,6 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
     auto old_car = [&](int k) {
       if (k < n_old) return colr[(size_t)k * 64];
       return make_float2(spawned_x(d, p.xs0, k - n_old), d.car_v);
-    };
-    auto idm = [&](float x, float v, float xl, float vl, float ll, float &xn, float &vn) {
-      const bool off_domain = __builtin_amdgcn_ballot_w64(!idm_fast_domain(v)) != 0ull;
-      if (d.fastdiv && !off_domain) idm_step_fast(d, x, v, xl, vl, ll, xn, vn);
-      else idm_step(d, x, v, xl, vl, ll, xn, vn);
     };
 
     bool open = true, far = false;
@@ -88,7 +79,7 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
         if (act) {
           const float2 c = old_car(k);
           float xn, vn;
-          idm(c.x, c.y, lx, lv, ll, xn, vn);
+          idm_plain(d, c.x, c.y, lx, lv, ll, xn, vn);
           open = xn > d.length;
           kpop += open ? 1 : 0;
           lx = c.x;
@@ -122,15 +113,14 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
     unsigned long long popmask = 0ull;
     float tail_x = 0.0f;
     bool has_tail = false;
-    // wrapped ring: x, not v, is tested on slots 1..lastcar (:210) = the cars from index kq on
-    const int kq = (p.ld > p.lc) ? C - 1 - p.ld : 0x7fffffff;
+    const int kq = kq_of(p, C);
 #pragma unroll
     for (int u = 0; u < KS; ++u) {
       const int k = k0 + u;
       if (k < k1 && k < n_tot) {
         const float x = cx[u], v = cv[u];
         float xn, vn;
-        idm(x, v, lx, lv, ll, xn, vn);
+        idm_plain(d, x, v, lx, lv, ll, xn, vn);
         cx[u] = xn;
         cv[u] = vn;
         lx = x;  // OLD state leads the next car (Jacobi)
@@ -141,9 +131,7 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
         if (pop) popmask |= 1ull << u;
         kpop += pop ? 1 : 0;
         far = far || (pop && ((xn - d.length) > d.length));
-        const float wq = (k >= kq) ? xn : vn;
-        n_wait += (wq < d.thresh) ? 1 : 0;
-        n_det += (xn > d.near_end) ? 1 : 0;
+        count_car(d, k, kq, xn, vn, n_wait, n_det);
         if (k == n_tot - 1) {
           tail_x = xn;
           has_tail = true;
@@ -193,27 +181,15 @@ __global__ __launch_bounds__(64 * S) void k_move_ts(const Dev d, const int tidx)
       }
       const int kpop_all = s_kpop[lane];
       if (p.n_tot != p.n_old) d.lastcar[id] = p.lc;
-      if (e < d.r) {
-        int *ob = d.obs + (size_t)env * d.obs_len;
-        if (n_tot > 0) {
-          d.waiting[(size_t)env * d.r + e] += tot_wait;
-          ob[d.r + e] = tot_det;
-        }
-        ob[e] = (d.agent_mode && tidx > 0) ? ob[e] + kpop_all : kpop_all;
-        if (kpop_all > 0) d.passed_dst[(size_t)env * d.I + e % d.I] = 1;
-      }
-      d.rec[id] = make_int4(rec_pack(kpop_all, p.ld, C), rec_y(p.ovf_sp, kpop_all > KP), __float_as_int(s_tail[lane]), n_tot);
-      d.leadx[id] = p.xL;
+      // (serial = false: every segment has stamped env_flag for itself above, the last one with the road's pop count)
+      store_tick_outputs(d, p, env, e, id, tick, n_tot, tot_wait, tot_det, kpop_all, s_tail[lane], 0, false,
+                         d.agent_mode && tidx > 0);
       my_updates += (unsigned long long)n_tot;
     }
     __syncthreads();  // the LDS words are free for the next tile
   }
 
-  if (seg == 0) {
-    for (int off = 32; off > 0; off >>= 1) my_updates += __shfl_down(my_updates, off);
-    if (lane == 0 && my_updates) veh_add(d.veh, my_updates);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) *d.tickB = tick;
+  finish_walk(d, lane, my_updates, tick, seg == 0);  // (only segment 0 counted)
 }
 
 }  // namespace tfx

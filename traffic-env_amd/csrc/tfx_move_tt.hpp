@@ -41,7 +41,7 @@
 #include <type_traits>
 
 #include "tfx_common.hpp"
-#include "tfx_move_t.hpp"
+#include "tfx_move_t.hpp"  // (and with it tfx_tile.hpp: the pieces these walkers share with k_move_t and k_move_ts)
 
 namespace tfx {
 
@@ -101,6 +101,8 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
                                             const bool skip = false) {
   constexpr int P = TT_P;
   const int C = d.C;
+  // (the lane's road, written out: through TileLane::road the plain one-tick forms take 65 and 87 registers for 63 and
+  // 86 and the heterogeneous forms move their scratch - tools/kernel_regs.py)
   const int e_slot = d.slot_road[(int)(tile - (long)env * d.G) * 64 + lane];
   const bool valid = e_slot >= 0;
   const int e = valid ? e_slot : 0;
@@ -127,13 +129,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   float *wcol = W ? d.w + ((size_t)tile * d.trows) * 64 + lane : nullptr;  // side words: same rows as the cars
   float *owcol = W ? d.outw + ((size_t)tile * KP) * 64 + lane : nullptr;
 
-  int kmax = n_old;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int o = __shfl_xor(kmax, off, 64);
-    kmax = o > kmax ? o : kmax;
-  }
-  kmax = __builtin_amdgcn_readfirstlane(kmax);
+  const int kmax = wave_max(n_old);
 
   float xprev = p.xL, vprev = 0.0f, llv = 0.0f;  // OLD state of the car ahead (Jacobi); starts as the fake leader
   float y1x = 0.0f, y1v = 0.0f, y2x = 0.0f, y2v = 0.0f;  // NEW states of cars k-1 and k-2
@@ -149,18 +145,8 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   unsigned wo = lo;  // where the next surviving car goes (byte offset from tb): one row further down per survivor
   int kq1 = 0x7fffffff;  // tick t+1 tests x instead of v from this car on (index of tick t)
   float tail_x = 0.0f, tail_z = 0.0f;
-  const int kq = (p.ld > p.lc) ? C - 1 - p.ld : 0x7fffffff;
+  const int kq = kq_of(p, C);
 
-  auto ld2 = [&](const float2 *ptr) {
-    const f2v t = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(ptr));
-    return make_float2(t.x, t.y);
-  };
-  auto st2 = [&](float2 *ptr, float a, float b) {
-    f2v t;
-    t.x = a;
-    t.y = b;
-    __builtin_nontemporal_store(t, reinterpret_cast<f2v *>(ptr));
-  };
   // Car k of this lane's road through tick t, car k-1 through tick t+1.  `last` (a compile-time flag): only
   // the second half, for the road's last car.
   auto step = [&](int k, float x, float v, float sw, auto last) {
@@ -187,13 +173,13 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
       if (TWO) idm_step(d, y1x, y1v, y2x, y2v, d.car_l, zx, zv);
     }
     if (TWO && two && pend) {  // car k-1: the new head keeps its tick-t state (k_edge moves it), the others are a tick ahead
-      st2(row_at(tb, 0, wo), pend_int ? zx : y1x, pend_int ? zv : y1v);
+      st_nt(row_at(tb, 0, wo), pend_int ? zx : y1x, pend_int ? zv : y1v);
       if (W) wcol[(wo - lo) >> 3] = y1w;
       wo += 512u;
       if (pend_int) {
-        const float wq1 = (k - 1 >= kq1) ? zx : zv;
-        n_wait += (wq1 < d.thresh) ? 1 : 0;
-        n_det2 += (zx > d.near_end) ? 0x10000 : 0;
+        int det1 = 0;
+        count_car(d, k - 1, kq1, zx, zv, n_wait, det1);
+        n_det2 += det1 << 16;
         if (LAST) tail_z = zx;  // (the road's last car is flushed by the LAST call)
       }
     }
@@ -209,7 +195,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
         *row_at(ox, 0, lo + (unsigned)kpop * 512u) = make_float2(xn, vn);
         if (W) owcol[(size_t)kpop * 64] = sw;
       } else {  // third pop: no survivor has been written yet - from here on every car stays in its row
-        st2(row_at(tb, (unsigned)k, lo), xn, vn);
+        st_nt(row_at(tb, (unsigned)k, lo), xn, vn);
         if (W) wcol[(size_t)k * 64] = sw;
         wo = lo + (unsigned)(k + 1) * 512u;
       }
@@ -219,14 +205,12 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
       pend_int = !was_open;
       if (was_open) kq1 = C - 1 - ring_adv(p.ld, kpop, C) + kpop;  // (kpop is final: this is the first survivor)
     } else {
-      st2(row_at(tb, 0, wo), xn, vn);
+      st_nt(row_at(tb, 0, wo), xn, vn);
       if (W) wcol[(wo - lo) >> 3] = sw;
       wo += 512u;
     }
     kpop += pop ? 1 : 0;  // (after the branches: they use the pops BEFORE this car)
-    const float wq = (k >= kq) ? xn : vn;
-    n_wait += (wq < d.thresh) ? 1 : 0;
-    n_det2 += (xn > d.near_end) ? 1 : 0;
+    count_car(d, k, kq, xn, vn, n_wait, n_det2);
     if (!TWO) tail_x = xn;  // (a pair: y1 holds the last car's new state when the walk ends)
     y2x = y1x;
     y2v = y1v;
@@ -245,7 +229,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   const float *wcolr = wcol + (size_t)hb * 64;
 #pragma unroll
   for (int u = 0; u < P; ++u) {
-    pf[u] = (u < n_old) ? ld2(row_at(tb, (unsigned)u, ro)) : make_float2(0.0f, 0.0f);
+    pf[u] = (u < n_old) ? ld_nt(row_at(tb, (unsigned)u, ro)) : make_float2(0.0f, 0.0f);
     pfw[u] = (W && u < n_old) ? wcolr[(size_t)u * 64] : 0.0f;
   }
   for (int k0 = 0; k0 < kmax; k0 += P) {
@@ -256,7 +240,7 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
         const float2 cur = pf[u];
         const float curw = pfw[u];
         if (k + P < kmax) {
-          pf[u] = (k + P < n_old) ? ld2(row_at(tb, (unsigned)(k + P), ro)) : make_float2(0.0f, 0.0f);
+          pf[u] = (k + P < n_old) ? ld_nt(row_at(tb, (unsigned)(k + P), ro)) : make_float2(0.0f, 0.0f);
           pfw[u] = (W && k + P < n_old) ? wcolr[(size_t)(k + P) * 64] : 0.0f;
         }
         if (k < n_old) step(k, cur.x, cur.y, curw, std::false_type{});
@@ -265,34 +249,10 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   }
   // ---- cars spawned this tick (add_car :97-114): they queue behind the tail ------------------
   if (__builtin_amdgcn_ballot_w64(n_sp > 0) != 0ull) {
-    int smax = n_sp;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o = __shfl_xor(smax, off, 64);
-      smax = o > smax ? o : smax;
-    }
-    smax = __builtin_amdgcn_readfirstlane(smax);
+    const int smax = wave_max(n_sp);
     if (HET) {
-      // add_car :97-114 car by car: each queues behind the road's tail at the moment it is created - the tail's
-      // OWN length and minimum gap - and brings the row add_new_cars drew for it (:164); as in k_move_t
-      int lcq = ring_adv(p.ld, n_old, C);
-      float tx = d.tailx[id];
-      int ta = d.taila[id];
-      const int ej = d.entry_idx[e];
-      const uint8_t *rows = (d.spawn_arch && d.spawn_mode == TFX_SPAWN_COUNTS && ej >= 0)
-                                ? d.spawn_arch + (size_t)tidx * d.spawn_arch_stride +
-                                      ((size_t)env * d.n_entry + ej) * d.spawn_arch_S
-                                : nullptr;
-      for (int s = 0; s < smax; ++s)
-        if (s < n_sp) {
-          const int row = (rows && s < d.spawn_arch_S) ? (rows[s] & (TFX_MAX_ARCH - 1)) : 0;
-          const float start = (lcq != p.ld) ? (tx - s_arch[ta * ARCH_W + AR_L]) - s_arch[ta * ARCH_W + AR_S0] : INFINITY;
-          const float xs = (start < 0.0f) ? start : 0.0f;
-          step(n_old + s, xs, s_arch[row * ARCH_W + AR_V], side_pack(tick, row), std::false_type{});
-          lcq = wrap1(lcq + 1, C);
-          tx = xs;
-          ta = row;
-        }
+      het_spawns(d, p, id, env, e, tick, tidx, n_old, n_sp, smax, s_arch,
+                 [&](int k, float x, float v, float sw) { step(k, x, v, sw, std::false_type{}); });
     } else {
       for (int s = 0; s < smax; ++s)
         if (s < n_sp) step(n_old + s, spawned_x(d, p.xs0, s), d.car_v, (float)tick, std::false_type{});
@@ -304,6 +264,8 @@ __device__ __forceinline__ int move_tt_tile(const Dev &d, const long tile, const
   }
 
   // ---- phase W -------------------------------------------------------------------------------
+  // (`!two` is store_tick_outputs' tick, tfx_tile.hpp, interleaved with the pair's record: split into the two arms, the
+  // agent forms, where `two` is known only at run time, carry the stores of both)
   if (run) {
     const int n_tot = p.n_tot;
     const int n_det = n_det2 & 0xffff, n_det1 = n_det2 >> 16;
@@ -349,7 +311,7 @@ __global__ __launch_bounds__(256) TT_ATTR(W, AGENT) void k_move_tt(const Dev d, 
   const int tick = *d.tickA;
   const long tiles = (long)d.E * d.G;
   const long nw = (long)gridDim.x * 4;
-  const int tick_sp = (d.spawn_mode == TFX_SPAWN_PERIODIC) ? tick % d.spawn_period : 0;
+  const int tick_sp = spawn_phase(d, tick);
 
   if (AGENT && only_risky && risk_any_word(d, tidx) != tick) return;  // (k_edge / k_tail has moved every other env and the clock)
 
@@ -371,9 +333,7 @@ __global__ __launch_bounds__(256) TT_ATTR(W, AGENT) void k_move_tt(const Dev d, 
                                                                             CREC && sorted_out);
   }
 
-  for (int off = 32; off > 0; off >>= 1) my_updates += __shfl_down(my_updates, off);
-  if (lane == 0 && my_updates) veh_add(d.veh, my_updates);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *d.tickB = tick;
+  finish_walk(d, lane, my_updates, tick);
 }
 
 // Could the tick starting at `tick` overflow a ring of this lane's road - or pop / hand over more cars than a pair's
@@ -383,10 +343,11 @@ __global__ __launch_bounds__(256) TT_ATTR(W, AGENT) void k_move_tt(const Dev d, 
 // road's first cars from the rows as they stand (after a pair: already at `tick`).
 __device__ __forceinline__ bool risk_lane(const Dev &d, long tile, int env, int lane, int tick, int tick_sp, int tidx) {
   const int C = d.C;
-  const int e = d.slot_road[(int)(tile - (long)env * d.G) * 64 + lane];
-  if (e < 0) return false;
+  TileLane tl;
+  tl.road(d, tile, env, lane);
+  if (!tl.valid) return false;
+  const int e = tl.e, id = tl.id;
   const float half_ar2 = (0.5f * (d.risk_a * d.rate)) * d.rate;
-  const int id = env * d.R + e;
   const int n = ring_count(d.leading[id], d.lastcar[id], C);
   const int ej = d.entry_idx[e];
   const int c_sp = ej >= 0 ? spawn_count(d, env, e, ej, tick_sp, tidx) : 0;
@@ -420,7 +381,7 @@ __global__ __launch_bounds__(256) void k_risk(const Dev d, const int tidx) {
   const int tick = *d.tickA;
   const long tiles = (long)d.E * d.G;
   const long nw = (long)gridDim.x * 4;
-  const int tick_sp = (d.spawn_mode == TFX_SPAWN_PERIODIC) ? tick % d.spawn_period : 0;
+  const int tick_sp = spawn_phase(d, tick);
   for (long tile = (long)blockIdx.x * 4 + wv; tile < tiles; tile += nw) {
     const int env = (int)(tile / d.G);
     if (env_frozen(d, env, tick)) continue;
@@ -446,9 +407,10 @@ __device__ __forceinline__ int edge_tile(const Dev &d, long tile, int env, int l
   // (agent step: frozen envs stand still; risky envs took the first tick alone and get the second from a
   // one-tick launch of their own)
   if (AGENT && (risk_word(d, env, tidx) == tick || env_frozen(d, env, tick))) return 0;
-  const int e = d.slot_road[(int)(tile - (long)env * d.G) * 64 + lane];
-  if (e < 0) return 0;
-  const int id = env * d.R + e;
+  TileLane tl;
+  tl.road(d, tile, env, lane);
+  if (!tl.valid) return 0;
+  const int e = tl.e, id = tl.id;
   const int4 rc = d.rec[id];    // the pass's record of the first tick
   const int r2c = d.rec2c[id];   // the road's waiting count of the first tick plus the second tick's so far | detected so far << 16
   const float2 r2f = d.rec2f[id];  // the tail's v after the first tick, its x after the second
@@ -456,10 +418,9 @@ __device__ __forceinline__ int edge_tile(const Dev &d, long tile, int env, int l
   const int m0 = rec_ntot(rc.w) - rec_kpop(rc.x);  // survivors of the first tick: rows 0 .. m0-1 (row 0 = the head)
   const int n_old = p.n_old, n_tot = p.n_tot;
 
-  float2 *col = d.xv + ((size_t)tile * d.trows) * 64 + lane;
-  float2 *ocol = d.outb + ((size_t)tile * KP) * 64 + lane;
-  float *wcol = W ? d.w + ((size_t)tile * d.trows) * 64 + lane : nullptr;
-  float *owcol = W ? d.outw + ((size_t)tile * KP) * 64 + lane : nullptr;
+  tl.columns<W>(d, tile, lane);
+  float2 *const col = tl.col, *const ocol = tl.ocol;
+  float *const wcol = tl.wcol, *const owcol = tl.owcol;
 
   int kpop = 0, n_wait = r2c & 1023, n_det = (r2c >> 10) & 511;
   bool open = true, far = false;
@@ -499,9 +460,7 @@ __device__ __forceinline__ int edge_tile(const Dev &d, long tile, int env, int l
     }
     if (pop) far = far || ((zx - d.length) > d.length);
     kpop += pop ? 1 : 0;
-    const float wq = (i >= kq) ? zx : zv;
-    n_wait += (wq < d.thresh) ? 1 : 0;
-    n_det += (zx > d.near_end) ? 1 : 0;
+    count_car(d, i, kq, zx, zv, n_wait, n_det);
     tail_x = zx;
   };
   if (m0 > 0) {
@@ -535,7 +494,9 @@ __device__ __forceinline__ int edge_tile(const Dev &d, long tile, int env, int l
     const float2 c = col[(size_t)i * 64];
     car(i, c.x, c.y, false);
   }
-  if (HET) {  // spawned this tick, car by car behind the tail's own length and gap (as in the pass)
+  // spawned this tick, car by car behind the tail's own length and gap: het_spawns' rule (tfx_tile.hpp), written out -
+  // through the helper k_tail<*, false, true, true> moves 4 to 8 bytes of its scratch
+  if (HET) {
     if (n_tot > n_old) {
       int lcq = ring_adv(p.ld, n_old, C);
       float tx = d.tailx[id];
@@ -596,15 +557,13 @@ __global__ __launch_bounds__(256) void k_edge(const Dev d, const int tidx) {
   const int tick = *d.tickA;
   const long tiles = (long)d.E * d.G;
   const long nw = (long)gridDim.x * 4;
-  const int tick_sp = (d.spawn_mode == TFX_SPAWN_PERIODIC) ? tick % d.spawn_period : 0;
+  const int tick_sp = spawn_phase(d, tick);
 
   unsigned long long my_updates = 0;
   for (long tile = (long)blockIdx.x * 4 + wv; tile < tiles; tile += nw)
     my_updates += (unsigned long long)edge_tile<AGENT, W, HET>(d, tile, (int)(tile / d.G), lane, tick, tick_sp, tidx, s_arch);
 
-  for (int off = 32; off > 0; off >>= 1) my_updates += __shfl_down(my_updates, off);
-  if (lane == 0 && my_updates) veh_add(d.veh, my_updates);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *d.tickB = tick;
+  finish_walk(d, lane, my_updates, tick);
 }
 
 }  // namespace tfx

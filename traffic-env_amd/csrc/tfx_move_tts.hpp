@@ -48,6 +48,8 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
   constexpr int P = TT_P;
   const int C = d.C;
   const int env = active ? (int)(tile / d.G) : 0;
+  // (the lane's road and, below, the tile's longest road are written out: through TileLane::road and wave_max the S = 2
+  // forms move 4 to 8 bytes of their scratch and two S = 4 / 8 forms a register - tools/kernel_regs.py)
   const int e_slot = active ? d.slot_road[(int)(tile - (long)env * d.G) * 64 + lane] : -1;
   const bool valid = e_slot >= 0;
   const int e = valid ? e_slot : 0;
@@ -60,12 +62,12 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
   const int n_old = run ? p.n_old : 0;
   const int n_tot = run ? p.n_tot : 0;
 
-  float2 *col = d.xv + ((size_t)(active ? tile : 0) * d.trows) * 64 + lane;
-  const float2 *colr = col + (size_t)hb * 64;
-  float2 *ocol = d.outb + ((size_t)(active ? tile : 0) * KP) * 64 + lane;
-  float *wcol = W ? d.w + ((size_t)(active ? tile : 0) * d.trows) * 64 + lane : nullptr;  // side words: same rows as col
+  TileLane tl;
+  tl.columns<W>(d, active ? tile : 0, lane);
+  float2 *const col = tl.col, *const ocol = tl.ocol;
+  float *const wcol = tl.wcol, *const owcol = tl.owcol;
+  const float2 *colr = col + (size_t)hb * 64;  // read: the live rows start hb rows down
   const float *wcolr = W ? wcol + (size_t)hb * 64 : nullptr;
-  float *owcol = W ? d.outw + ((size_t)(active ? tile : 0) * KP) * 64 + lane : nullptr;
 
   int kmax = n_tot;
 #pragma unroll
@@ -82,21 +84,12 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
   const int k_lo = h < kmax ? h : kmax;
   const int k_hi = (h + kseg < kmax) ? h + kseg : kmax;
 
-  auto ld2 = [&](const float2 *ptr) {
-    const f2v t = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(ptr));
-    return make_float2(t.x, t.y);
-  };
   // old state of car k: a row of the column, or a car spawned this tick queueing behind the tail (:97-114)
   auto old_car = [&](int k) {
-    if (k < n_old) return ld2(&colr[(size_t)k * 64]);
+    if (k < n_old) return ld_nt(&colr[(size_t)k * 64]);
     return make_float2(spawned_x(d, p.xs0, k - n_old), d.car_v);
   };
   auto old_w = [&](int k) { return (W && k < n_old) ? wcolr[(size_t)k * 64] : (float)tick; };  // spawned this tick: w = tick
-  auto idm = [&](float x, float v, float xl, float vl, float ll, float &xn, float &vn) {
-    const bool off_domain = __builtin_amdgcn_ballot_w64(!idm_fast_domain(v)) != 0ull;
-    if (d.fastdiv && !off_domain) idm_step_fast(d, x, v, xl, vl, ll, xn, vn);
-    else idm_step(d, x, v, xl, vl, ll, xn, vn);
-  };
 
   float xprev = p.xL, vprev = 0.0f, llv = 0.0f;  // OLD state of the car ahead (Jacobi); starts as the fake leader
   float y1x = 0.0f, y1v = 0.0f, y2x = 0.0f, y2v = 0.0f;  // NEW states of cars k-1 and k-2
@@ -106,7 +99,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
   bool pend = false, pend_int = false;
   int kq1 = 0x7fffffff;
   float tail_z = 0.0f;
-  const int kq = (p.ld > p.lc) ? C - 1 - p.ld : 0x7fffffff;
+  const int kq = kq_of(p, C);
   const bool mine = n_tot > k_lo;  // this lane's road has cars in this segment's range
 
   if (seg > 0) {
@@ -117,7 +110,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
       if (act) {
         const float2 c = old_car(k);
         float xn, vn;
-        idm(c.x, c.y, xprev, vprev, llv, xn, vn);
+        idm_plain(d, c.x, c.y, xprev, vprev, llv, xn, vn);
         open = xn > d.length;
         kpop += open ? 1 : 0;
         xprev = c.x;
@@ -134,7 +127,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
       float xn = 0.0f, vn = 0.0f;
       // (car h-2's leader plays no part: only car h-1's new state is needed; while `open` holds car h-1 popped and car h
       // is the road's new head - its second tick is the edge work's, no leader state is read)
-      idm(c1.x, c1.y, c2.x, c2.y, d.car_l, xn, vn);
+      idm_plain(d, c1.x, c1.y, c2.x, c2.y, d.car_l, xn, vn);
       if (mine) {
         xprev = c1.x;
         vprev = c1.y;
@@ -175,10 +168,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
       ++n_hold;
       return;
     }
-    f2v t;
-    t.x = a;
-    t.y = b;
-    __builtin_nontemporal_store(t, reinterpret_cast<f2v *>(ptr));
+    st_nt(ptr, a, b);
     if (W) wcol[ptr - col] = sw;
   };
 
@@ -199,9 +189,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
       st2(wp, pend_int ? zx : y1x, pend_int ? zv : y1v, y1w);
       wp += 64;
       if (pend_int) {
-        const float wq1 = (k - 1 >= kq1) ? zx : zv;
-        n_wait1 += (wq1 < d.thresh) ? 1 : 0;
-        n_det1 += (zx > d.near_end) ? 1 : 0;
+        count_car(d, k - 1, kq1, zx, zv, n_wait1, n_det1);
         if (mode == 1) tail_z = zx;
       }
     }
@@ -230,9 +218,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
       st2(wp, xn, vn, sw);
       wp += 64;
     }
-    const float wq = (k >= kq) ? xn : vn;
-    n_wait += (wq < d.thresh) ? 1 : 0;
-    n_det += (xn > d.near_end) ? 1 : 0;
+    count_car(d, k, kq, xn, vn, n_wait, n_det);
     y2x = y1x;
     y2v = y1v;
     y1x = xn;
@@ -246,7 +232,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
 #pragma unroll
   for (int u = 0; u < P; ++u) {
     const bool in = k_lo + u < n_old && k_lo + u < k_hi;
-    pf[u] = in ? ld2(&colr[(size_t)(k_lo + u) * 64]) : make_float2(0.0f, 0.0f);
+    pf[u] = in ? ld_nt(&colr[(size_t)(k_lo + u) * 64]) : make_float2(0.0f, 0.0f);
     if (W) pfw[u] = in ? wcolr[(size_t)(k_lo + u) * 64] : 0.0f;
   }
   for (int k0 = k_lo; k0 < k_hi; k0 += P) {
@@ -257,7 +243,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
         const float2 cur = pf[u];
         const float curw = W ? pfw[u] : 0.0f;
         if (k + P < k_hi) {
-          pf[u] = (k + P < n_old) ? ld2(&colr[(size_t)(k + P) * 64]) : make_float2(0.0f, 0.0f);
+          pf[u] = (k + P < n_old) ? ld_nt(&colr[(size_t)(k + P) * 64]) : make_float2(0.0f, 0.0f);
           if (W) pfw[u] = (k + P < n_old) ? wcolr[(size_t)(k + P) * 64] : 0.0f;
         }
         if (k < n_old) step(k, cur.x, cur.y, curw, 0);
@@ -293,10 +279,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
 #pragma unroll
     for (int q = 0; q < TTS_HOLD; ++q)
       if (q < n_hold) {
-        f2v t;
-        t.x = hold[q].x;
-        t.y = hold[q].y;
-        __builtin_nontemporal_store(t, reinterpret_cast<f2v *>(hold_first + (size_t)q * 64));
+        st_nt(hold_first + (size_t)q * 64, hold[q].x, hold[q].y);
         if (W) wcol[(hold_first - col) + (size_t)q * 64] = hold_w[q];
       }
     return 0;
@@ -320,7 +303,7 @@ __device__ __forceinline__ int move_tt_tile_seg(const Dev &d, const long tile, c
       }
     }
   }
-  // ---- phase W (move_tt_tile's, plain cars) -------------------------------------------------------------------------
+  // ---- phase W (move_tt_tile's, plain cars; `!two` is store_tick_outputs' tick, interleaved as there) ---------------
   if (e < d.r) {
     int *ob = d.obs + (size_t)env * d.obs_len;
     if (n_tot > 0 && !two) {  // (a pair: edge_tile adds both ticks' waiting counts at once and stores `detected`)
@@ -361,7 +344,7 @@ void k_move_tts(const Dev d, const int tidx) {
   const int tick = *d.tickA;
   const long tiles = (long)d.E * d.G;
   const long n_groups = (tiles + TPW - 1) / TPW;
-  const int tick_sp = (d.spawn_mode == TFX_SPAWN_PERIODIC) ? tick % d.spawn_period : 0;
+  const int tick_sp = spawn_phase(d, tick);
   unsigned long long my_updates = 0;
   for (long pr = blockIdx.x; pr < n_groups; pr += gridDim.x) {
     const long tile = pr * TPW + tl;
@@ -376,9 +359,7 @@ void k_move_tts(const Dev d, const int tidx) {
                                                                           CREC && sorted_out);
     __syncthreads();  // (the LDS words are free for the next tiles)
   }
-  for (int off = 32; off > 0; off >>= 1) my_updates += __shfl_down(my_updates, off);
-  if (lane == 0 && my_updates) veh_add(d.veh, my_updates);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *d.tickB = tick;
+  finish_walk(d, lane, my_updates, tick);
 }
 
 }  // namespace tfx

@@ -8,11 +8,11 @@
 //     no cars), and so does every lane of an env that is not shown: of such an env nothing but slot_road is read.
 //     Everything a lane knows of its item is in the TileRoad it gets here, so nothing carries over from one item of the
 //     stride loop to the next.
-//   * walk_cars, transposed layout: the wavefront reduces the tile's deepest live row, kmax; rows 0 .. kmax-1 are walked
-//     as coalesced row loads (64 x 8 B of (x, v), 64 x 4 B of side words), WALK_P rows in flight, default caching.  A
-//     lane loads rows hb <= k < hb + n of its own column and no others - not the rows a two-tick pass left empty at the
-//     top of the column (hb, tfx_move_tt.hpp), not the rows past the road's count - so a sparse env costs less than a
-//     full one.
+//   * walk_cars, transposed layout: the wavefront reduces the tile's deepest live row, kmax (wave_max, which the move
+//     kernels' tile walkers share: tfx_tile.hpp); rows 0 .. kmax-1 are walked as coalesced row loads (64 x 8 B of
+//     (x, v), 64 x 4 B of side words), WALK_P rows in flight, default caching.  A lane loads rows hb <= k < hb + n of
+//     its own column and no others - not the rows a two-tick pass left empty at the top of the column (hb,
+//     tfx_move_tt.hpp), not the rows past the road's count - so a sparse env costs less than a full one.
 //   * walk_cars, ring layout (tfx_config.layout = 0, the non-default one): each lane walks the ring slots of its road
 //     from leading + 1 with wrap1.
 //   * Either way `visit` sees a road's cars from the head to the tail: float32 sums taken in that order are
@@ -26,16 +26,6 @@
 namespace tfx {
 
 constexpr int WALK_P = 8;  // rows in flight per wavefront
-
-// the largest v of the wavefront's 64 lanes, wave-uniform
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int q = __shfl_xor(v, off, 64);
-    v = q > v ? q : v;
-  }
-  return __builtin_amdgcn_readfirstlane(v);
-}
 
 // what a lane knows of its road of an item
 struct TileRoad {
