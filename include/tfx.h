@@ -418,6 +418,18 @@ int tfx_xv_pairs(tfx_handle h, int64_t *pairs);
  * tfx_refresh. */
 int tfx_export_ring(tfx_handle h, float *ring_xv, float *ring_w, uint8_t *ring_a, void *stream);
 int tfx_import_ring(tfx_handle h, const float *ring_xv, const float *ring_w, const uint8_t *ring_a, void *stream);
+/* What the next call depends on.  The results of the next tfx_step / tfx_agent_step / tfx_move_cars +
+ * tfx_advance_finished_cars depend on four things only: the ring image (the cars as tfx_export_ring shows them, leading,
+ * lastcar), the other bound buffers (obs, rewards, waiting, passed_dst, done_tick, the trip log), the clock
+ * (tfx_get_tick) and the inputs bound for the call.  A handle that has run anything before and a new one that was
+ * given the same four (tfx_reset, the buffers copied, tfx_import_ring + tfx_refresh, tfx_set_tick, then done_tick -
+ * tfx_set_tick clears it) compute the same bits from then on; importing a handle's own export changes nothing.  Three
+ * things the handle owns and the caller cannot export travel through tfx_clone_envs alone: the position of an on-device
+ * arrival stream (TFX_CLONE_STREAM), the greedy controller's held action, and the episode marks and accounting
+ * (TFX_CLONE_EPISODE).  Everything else a handle keeps between calls - row offsets of the two-tick pass, tail and
+ * record caches, the stamps of overflows, of the serial advance and of the risk bound, the second stream's clock, its
+ * captured graphs - is rebuilt or ignored: a stamp left by an earlier call may cost time (an env takes the exact serial
+ * or one-tick form once more), it never changes a result.  tests/test_gpu_transplant.py holds every step path to this. */
 
 /* Two of the IDM's three divisions have a constant divisor (2*sqrt(a*b) and v0).  At tfx_create the
  * library checks on the device, exhaustively over the admitted numerator range, that the

@@ -137,10 +137,9 @@ def load_oracle(orc, x, v, w, leading, lastcar):
     np.put_along_axis(orc.state[:, :, XI, :], ld, np.take_along_axis(np.asarray(x, np.float32), ld, axis=2), axis=2)
 
 
-def grid_tables():
-    """dest, phases, nexts and the entry roads of the 6x5 grid, built as csrc/tfx_handle.hpp:build_tables does
-    (roadgraph.py:26-64) - the CPU tests have no handle to ask"""
-    m, n = M, N
+def grid_tables(m=M, n=N):
+    """dest, phases, nexts and the entry roads of the m x n grid (default: the 6x5 one), built as
+    csrc/tfx_handle.hpp:build_tables does (roadgraph.py:26-64) - the CPU tests have no handle to ask"""
     I = m * n
     r = 4 * I
     R = r + 2 * m + 2 * n
