@@ -812,6 +812,57 @@ int tfx_road_following(tfx_handle h, const tfx_follow_params *p, const tfx_follo
 /* Test support: the launch geometry tfx_road_following uses for this handle - workgroups, and wavefronts (one per
  * (env, tile) item at a time), like tfx_measure_launch. */
 int tfx_follow_launch(tfx_handle h, int32_t *grid, int32_t *waves);
+/* Road ends on the device: the first K cars at every stop line and the last car of every road, from one read-only launch
+ * (k_ends, csrc/tfx_ends.hpp).  Every other road call reduces a road to a few numbers; this one hands out the cars
+ * themselves, where a policy looks: the nearest vehicles of an approach as (distance to the stop line, speed) - what an
+ * attention-style or an actuated signal controller reads - and where the last car of a road stands, which is the room
+ * left at its entrance.  The head car against the stop line and against the last car of the road it drives into are the
+ * pairs tfx_road_following leaves out.  The launch reads at most K + 2 rows of a tile and one more for the tails, whatever
+ * the density.  Without this call the route is tfx_export_ring of every ring slot.
+ *
+ * Definition, as a function of the image tfx_export_ring would produce at that moment (on a ring-layout handle: of xv
+ * itself): between two-tick passes, after a clone, between tfx_move_cars and tfx_advance_finished_cars.  For road e of env
+ * k: n = ring_count(leading, lastcar) clamped to 0 .. C-1, what tfx_cars_on_roads returns; car j (0 <= j < n) sits in ring
+ * slot wrap(leading + 1 + j).  Cars are listed in ring order, head first, as exported - NOT sorted by x: an unsorted ring
+ * and a car past the road end give what their slots hold.  With k = K in 1 .. TFX_MAX_HEADS:
+ *   n_cars     int32 [E][R]         n
+ *   n_heads    int32 [E][R]         min(n, K)
+ *   heads      float32 [E][R][K][2] entry j < min(n, K): (length - x_j, v_j) - ONE float32 subtraction from
+ *                                   tfx_config.length, negative for a car past the road end; the others (pad_dist, pad_v)
+ *   head_rows  uint8 [E][R][K]      the archetype row of car j (the low 6 bits of its side word's integer bits) on
+ *                                   heterogeneous handles, 0 on single-archetype handles; TFX_ENDS_NO_CAR in padded entries
+ *   tail       float32 [E][R][2]    (x, v) of car n - 1; (pad_tail_x, pad_v) on an empty road
+ *   tail_row   uint8 [E][R]         the row of car n - 1, TFX_ENDS_NO_CAR on an empty road
+ * All by the reference's road id, over all R roads.  The pads may be any float32, infinities and NaN included: they are
+ * stored bit for bit.  Outputs are device pointers (heads and tail 8-byte aligned); any may be NULL and is then skipped.
+ * Lists do not add: there is no accumulate form, flags must be 0.  Ages of the listed cars (tfx_car_ages has the per-road
+ * figures), a range filter (callers mask by distance) and sorting by x are out of scope.
+ *
+ * One launch on `stream`, no host synchronisation; nothing in the handle or in the caller's bound state is written:
+ * captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the launch.  TFX_MEASURE_GRID and
+ * TFX_GRID_CAP cap the launch as they cap the measures'.  TFX_EINVAL: a NULL handle, a NULL `p` or `out`, k outside
+ * 1 .. TFX_MAX_HEADS, flags other than 0; TFX_ESTATE before tfx_bind_buffers.  A refused call launches nothing.
+ * gym_traffic/devrng.py road_ends states the definition in NumPy. */
+#define TFX_MAX_HEADS 16
+#define TFX_ENDS_NO_CAR 255
+typedef struct tfx_ends_params {
+  int32_t k;           /* cars listed from the head of every road, 1 .. TFX_MAX_HEADS */
+  float pad_dist;      /* distance of a padded heads entry */
+  float pad_v;         /* speed of a padded heads entry and of the tail of an empty road */
+  float pad_tail_x;    /* x of the tail of an empty road */
+} tfx_ends_params;
+typedef struct tfx_ends_buffers {
+  int32_t *n_cars;     /* [E][R] by road id; any may be NULL */
+  int32_t *n_heads;
+  float *heads;        /* [E][R][k][2] */
+  uint8_t *head_rows;  /* [E][R][k] */
+  float *tail;         /* [E][R][2] */
+  uint8_t *tail_row;   /* [E][R] */
+} tfx_ends_buffers;
+int tfx_road_ends(tfx_handle h, const tfx_ends_params *p, const tfx_ends_buffers *out, int32_t flags, void *stream);
+/* Test support: the launch geometry tfx_road_ends uses for this handle and k - workgroups, and wavefronts (one per
+ * (env, tile) item at a time), like tfx_follow_launch. */
+int tfx_ends_launch(tfx_handle h, int32_t k, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

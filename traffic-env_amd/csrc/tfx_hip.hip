@@ -22,6 +22,7 @@
 
 #include "tfx_cells.hpp"
 #include "tfx_follow.hpp"
+#include "tfx_ends.hpp"
 #include "tfx_frames.hpp"
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
@@ -1217,6 +1218,31 @@ int tfx_road_following(tfx_handle h, const tfx_follow_params *p, const tfx_follo
 
 int tfx_follow_launch(tfx_handle h, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
+  return report_launch(tile_grid(h, true), grid, waves);
+}
+
+int tfx_road_ends(tfx_handle h, const tfx_ends_params *p, const tfx_ends_buffers *out, int32_t flags, void *stream) {
+  if (!p) return fail(TFX_EINVAL, "ends: p is null");
+  if (!out) return fail(TFX_EINVAL, "ends: out is null");
+  if (int rc = check_handle(h, false)) return rc;
+  if (p->k < 1 || p->k > TFX_MAX_HEADS) return fail(TFX_EINVAL, "ends: k %d is outside 1..%d", p->k, TFX_MAX_HEADS);
+  if (flags) return fail(TFX_EINVAL, "unknown ends flags 0x%x (lists do not accumulate)", flags);
+  if (int rc = check_handle(h, true)) return rc;
+  EndsOut o{};
+  o.n_cars = out->n_cars;
+  o.n_heads = out->n_heads;
+  o.heads = reinterpret_cast<f2v *>(out->heads);
+  o.head_rows = out->head_rows;
+  o.tail = reinterpret_cast<f2v *>(out->tail);
+  o.tail_row = out->tail_row;
+  // k_measure's launch (tile_grid), instantiated on the bound of k
+  const int K = p->k;
+  return launch_query(K <= 4 ? k_ends<4> : K <= 8 ? k_ends<8> : k_ends<16>, tile_grid(h, true), stream, h->d, *p, o);
+}
+
+int tfx_ends_launch(tfx_handle h, int32_t k, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (k < 1 || k > TFX_MAX_HEADS) return fail(TFX_EINVAL, "ends: k %d is outside 1..%d", k, TFX_MAX_HEADS);
   return report_launch(tile_grid(h, true), grid, waves);
 }
 

@@ -1,5 +1,6 @@
 // tfx_walk.hpp - the one walk of the live cars that the read-only road kernels share: k_measure (tfx_measure.hpp),
-// k_cells (tfx_cells.hpp), k_ages (tfx_travel.hpp), k_frames (tfx_frames.hpp) and k_follow (tfx_follow.hpp).  Device only.
+// k_cells (tfx_cells.hpp), k_ages (tfx_travel.hpp), k_frames (tfx_frames.hpp), k_follow (tfx_follow.hpp) and k_ends
+// (tfx_ends.hpp, which cuts the walk short: it hands in a TileRoad whose count is clamped to its K).  Device only.
 //
 // The kernels take one wavefront per (env or frame, tile) item, four to a workgroup, striding over the items, lane per
 // road as in k_move_t (tfx_move_t.hpp):

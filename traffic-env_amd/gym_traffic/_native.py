@@ -18,6 +18,8 @@ TRAVEL_ACCUMULATE = 1                   # flag of tfx_car_ages and tfx_trip_stat
 MAX_TRIP_BINS = 32                      # the most bins tfx_trip_stats takes
 FRAMES_ROADS_ONLY = 1                   # flag of tfx_frames
 FOLLOW_ACCUMULATE = 1                   # flag of tfx_road_following
+MAX_HEADS = 16                          # TFX_MAX_HEADS: the most cars tfx_road_ends lists per road
+ENDS_NO_CAR = 255                       # TFX_ENDS_NO_CAR: the row of a padded entry
 FRAME_PX_MIN, FRAME_PX_MAX = 8, 256     # TFX_FRAME_PX_MIN, TFX_FRAME_PX_MAX
 DEMAND_MAX_PROFILES, DEMAND_MAX_SEGMENTS, DEMAND_MAX_CDF = 16, 64, 256   # limits of tfx_set_demand
 
@@ -72,6 +74,15 @@ class TfxFollowBuffers(C.Structure):
     _fields_ = [("n_cars", C.c_void_p), ("n_pairs", C.c_void_p), ("n_joined", C.c_void_p), ("n_overlap", C.c_void_p),
                 ("gap_sum", C.c_void_p), ("gap_min", C.c_void_p), ("n_hw", C.c_void_p), ("hw_sum", C.c_void_p),
                 ("n_conflict", C.c_void_p), ("ttc_min", C.c_void_p), ("drac_max", C.c_void_p)]
+
+
+class TfxEndsParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("pad_dist", C.c_float), ("pad_v", C.c_float), ("pad_tail_x", C.c_float)]
+
+
+class TfxEndsBuffers(C.Structure):
+    _fields_ = [("n_cars", C.c_void_p), ("n_heads", C.c_void_p), ("heads", C.c_void_p), ("head_rows", C.c_void_p),
+                ("tail", C.c_void_p), ("tail_row", C.c_void_p)]
 
 
 class TfxDemand(C.Structure):
@@ -157,6 +168,8 @@ _PROTOS = {
     "tfx_road_following": (C.c_int, [C.c_void_p, C.POINTER(TfxFollowParams), C.POINTER(TfxFollowBuffers), C.c_int32,
                                      C.c_void_p]),
     "tfx_follow_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_road_ends": (C.c_int, [C.c_void_p, C.POINTER(TfxEndsParams), C.POINTER(TfxEndsBuffers), C.c_int32, C.c_void_p]),
+    "tfx_ends_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

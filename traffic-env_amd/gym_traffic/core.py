@@ -41,6 +41,9 @@ TripStats = collections.namedtuple("TripStats", "count tick_sum tick_max lost hi
 RoadFollowing = collections.namedtuple("RoadFollowing", "n_cars n_pairs n_joined n_overlap gap_sum gap_min n_hw hw_sum "
                                                         "n_conflict ttc_min drac_max")
 _FOLLOW_FLOATS = ("gap_sum", "gap_min", "hw_sum", "ttc_min", "drac_max")
+# what road_ends() returns: n_cars, n_heads int32 [E, R]; heads float32 [E, R, k, 2]; head_rows uint8 [E, R, k]; tail
+# float32 [E, R, 2]; tail_row uint8 [E, R] - device tensors by road id (tfx_road_ends, include/tfx.h)
+RoadEnds = collections.namedtuple("RoadEnds", "n_cars n_heads heads head_rows tail tail_row")
 
 
 def _ptr(t):
@@ -215,6 +218,7 @@ class TfxEngine(object):
         self._following = None      # road_following(): made on first use
         self._trips = {}            # trip_stats(): made on first use, per number of bins
         self._cells = {}            # road_cells(): made on first use, per number of cells
+        self._ends = {}             # road_ends(): made on first use, per k
         self._frames = {}           # frames(): made on first use, per (frames, px); holds the background after that
         b = nat.TfxBuffers()
         b.xv = _ptr(self._t if self._t is not None else self._ring)
@@ -496,6 +500,44 @@ class TfxEngine(object):
         """(workgroups, wavefronts) of the road_following launch of this engine (tfx_follow_launch; tests)."""
         g, w = C.c_int32(), C.c_int32()
         nat.check(self.lib.tfx_follow_launch(self.h, C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def road_ends(self, k=4, pad_dist=float("inf"), pad_v=0.0, pad_tail_x=float("inf"), out=None):
+        """The two ends of every road, from one read-only launch (tfx_road_ends, include/tfx.h; gym_traffic.devrng.road_ends
+        states the definition in NumPy): -> RoadEnds(n_cars, n_heads int32 [E, R]; heads float32 [E, R, k, 2]; head_rows
+        uint8 [E, R, k]; tail float32 [E, R, 2]; tail_row uint8 [E, R]), device tensors by road id.  heads[..., j, :] is
+        (length - x, v) of car j from the head, in ring order, for j < min(n, k) and (pad_dist, pad_v) beyond; tail is
+        (x, v) of the road's last car, (pad_tail_x, pad_v) on an empty road; the rows are the cars' archetype rows (0 on
+        single-archetype engines), 255 where there is no car.  k: 1 .. 16.  out: the caller's RoadEnds (any member None:
+        not computed); default: tensors the engine allocates once per k and reuses.  No host synchronisation; nothing of
+        the env state is written."""
+        k = int(k)
+        if not 1 <= k <= nat.MAX_HEADS:
+            raise ValueError("road_ends: k %d is outside 1..%d" % (k, nat.MAX_HEADS))
+        E, R = self.E, self.R
+        want = dict(n_cars=(torch.int32, (E, R)), n_heads=(torch.int32, (E, R)), heads=(torch.float32, (E, R, k, 2)),
+                    head_rows=(torch.uint8, (E, R, k)), tail=(torch.float32, (E, R, 2)), tail_row=(torch.uint8, (E, R)))
+        if out is None:
+            if k not in self._ends:
+                self._ends[k] = RoadEnds(*[torch.zeros(want[f][1], dtype=want[f][0], device=self.device)
+                                           for f in RoadEnds._fields])
+            out = self._ends[k]
+        else:
+            out = RoadEnds(*out)
+            for name, t in zip(RoadEnds._fields, out):
+                dtype, shape = want[name]
+                if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                    raise ValueError("road_ends(out=): %s must be a contiguous %s %s device tensor" % (name, dtype, list(shape)))
+        p = nat.TfxEndsParams(k, float(pad_dist), float(pad_v), float(pad_tail_x))
+        b = nat.TfxEndsBuffers(*[_ptr(t) for t in out])
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_road_ends(self.h, C.byref(p), C.byref(b), 0, self._stream()))
+        return out
+
+    def ends_launch(self, k):
+        """(workgroups, wavefronts) of the road_ends launch of this engine for k cars a road (tfx_ends_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_ends_launch(self.h, int(k), C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
 
     def car_ages(self, accumulate=False, out=None):

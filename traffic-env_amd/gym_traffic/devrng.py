@@ -240,6 +240,61 @@ def road_following(x, v, leading, lastcar, C, params, car_l=4.0, arch_rows=None,
     return tuple(a.reshape(shape) for a in out)
 
 
+ENDS_FIELDS = ("n_cars", "n_heads", "heads", "head_rows", "tail", "tail_row")
+ENDS_NO_CAR = 255     # TFX_ENDS_NO_CAR
+
+
+def road_ends(x, v, leading, lastcar, C, length, k, pad_dist, pad_v, pad_tail_x, arch=None):
+    """The definition of tfx_road_ends (include/tfx.h) in NumPy, over ring planes: x, v float32 [..., R, C] by ring slot
+    (what tfx_export_ring produces), leading / lastcar int [..., R]; arch uint8 [..., R, C]: the archetype row of every
+    ring slot on heterogeneous handles (None: every row is 0).  -> a tuple in the order of ENDS_FIELDS: n_cars, n_heads
+    int32 [..., R]; heads float32 [..., R, k, 2]; head_rows uint8 [..., R, k]; tail float32 [..., R, 2]; tail_row uint8
+    [..., R].  n is the ring count clamped to 0 .. C-1; car j of a road (j = 0: the head) sits in slot
+    wrap(leading + 1 + j) - ring order, never sorted by x.  heads[j] = (float32(length) - x_j, v_j) for j < min(n, k) and
+    (pad_dist, pad_v) beyond, rows ENDS_NO_CAR there; tail = (x, v) of car n - 1, or (pad_tail_x, pad_v) and row
+    ENDS_NO_CAR on an empty road.  The pads are stored as given, bit for bit (NaN payloads included)."""
+    C, k = int(C), int(k)
+    if not 1 <= k <= 16:
+        raise ValueError("road_ends: k %d is outside 1..16" % k)
+    x = np.asarray(x, np.float32)
+    v = np.asarray(v, np.float32)
+    shape = x.shape[:-1]
+    x, v = x.reshape(-1, C), v.reshape(-1, C)
+    ld = np.asarray(leading, np.int64).reshape(-1)
+    lc = np.asarray(lastcar, np.int64).reshape(-1)
+    n = np.clip(lc - ld + np.where(ld > lc, C - 1, 0), 0, C - 1)
+    N = len(ld)
+    roads = np.arange(N)
+    rows = np.zeros((N, C), np.uint8) if arch is None else np.asarray(arch, np.uint8).reshape(-1, C)
+    L = np.float32(length)
+    pads = np.array([pad_dist, pad_v, pad_tail_x], np.float32)      # (an array keeps a NaN's bits; a scalar may not)
+    heads = np.empty((N, k, 2), np.float32)
+    heads[..., 0], heads[..., 1] = pads[0], pads[1]
+    head_rows = np.full((N, k), ENDS_NO_CAR, np.uint8)
+
+    def slot_of(j):
+        s = ld + 1 + j
+        return np.where(s > C - 1, s - (C - 1), s)
+
+    for j in range(k):
+        live = j < n
+        slot = np.where(live, slot_of(j), 0)
+        with np.errstate(invalid="ignore"):
+            dist = (L - x[roads, slot]).astype(np.float32)           # one float32 subtraction
+        heads[live, j, 0] = dist[live]
+        heads[live, j, 1] = v[roads, slot][live]
+        head_rows[live, j] = rows[roads, slot][live]
+    some = n > 0
+    slot = np.where(some, slot_of(n - 1), 0)
+    tail = np.empty((N, 2), np.float32)
+    tail[:, 0], tail[:, 1] = pads[2], pads[1]
+    tail[some, 0], tail[some, 1] = x[roads, slot][some], v[roads, slot][some]
+    tail_row = np.where(some, rows[roads, slot], ENDS_NO_CAR).astype(np.uint8)
+    return (n.astype(np.int32).reshape(shape), np.minimum(n, k).astype(np.int32).reshape(shape),
+            heads.reshape(shape + (k, 2)), head_rows.reshape(shape + (k,)), tail.reshape(shape + (2,)),
+            tail_row.reshape(shape))
+
+
 def car_ages(w, leading, lastcar, C, now, het=False):
     """The definition of tfx_car_ages (include/tfx.h) in NumPy, over the ring plane w float32 [..., R, C] of spawn ticks
     by ring slot (what tfx_export_ring produces; heterogeneous handles: the spawn tick modulo 2^24), leading / lastcar

@@ -59,6 +59,9 @@ VecMeasures = collections.namedtuple("VecMeasures", "n_cars n_halted queue speed
 VecFollowing = collections.namedtuple("VecFollowing", "n_cars n_pairs n_joined n_overlap gap_sum gap_min n_hw hw_sum n_conflict "
                                                       "ttc_min drac_max pairs mean_gap min_gap platoons mean_platoon_size "
                                                       "mean_headway_s min_ttc_s conflicts max_drac overlaps")
+# what TrafficVecEnv.stop_lines() returns: the engine's six road-end tensors and the views derived from them
+VecEnds = collections.namedtuple("VecEnds", "n_cars n_heads heads head_rows tail tail_row approach eta_s entry_room "
+                                            "downstream_room cross_gap")
 # what TrafficVecEnv.cell_obs() returns: the engine's two per-cell tensors and the image a convolutional policy reads
 VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
 # what TrafficVecEnv.travel_times() returns: per-env travel-time figures, finished trips and cars still on the map
@@ -529,6 +532,51 @@ class TrafficVecEnv(object):
                             ratio(rf.hw_sum[:, :r].sum(dim=1, dtype=torch.float64), total(rf.n_hw)),
                             rf.ttc_min[:, :r].min(dim=1).values, total(rf.n_conflict),
                             rf.drac_max[:, :r].max(dim=1).values, total(rf.n_overlap))
+
+    def stop_lines(self, k=4, v_min=0.5):
+        """The cars at every stop line and the room at every road's entrance, on the device, with no host
+        synchronisation: one read-only launch that reads the first k cars and the last car of every road
+        (TfxEngine.road_ends / tfx_road_ends, include/tfx.h) plus a few torch expressions.  -> VecEnds:
+            n_cars, n_heads int32 [E, R]; heads float32 [E, R, k, 2]; head_rows uint8 [E, R, k]; tail float32 [E, R, 2];
+                        tail_row uint8 [E, R] - per road id: the engine's tensors for this k, overwritten by the next
+                        call with the same k.  heads[..., j, :] is (distance to the stop line, speed) of car j from the
+                        head, (+inf, 0) where the road has fewer cars; tail is (x, v) of the last car, (+inf, 0) on an
+                        empty road; the rows are archetype rows, 255 where there is no car
+            approach    float32 [E, m, n, 4, k, 2] - heads of the train roads in cars_on_roads()' order: [:, row, col, d]
+                        is the approach of direction d into intersection (row, col), what a per-intersection policy reads
+            eta_s       float32 [E, r, k] - distance / max(speed, v_min): seconds to the stop line at the car's current
+                        speed (never faster than a car of speed v_min); +inf where padded
+            entry_room  float32 [E, R] - tail x - l, l the last car's length (its archetype row's; the single
+                        archetype's otherwise): the free road behind the last car, +inf on an empty road
+            downstream_room float32 [E, r] - entry_room of the road a train road's cars drive into (graph.nexts), +inf
+                        where there is none
+            cross_gap   float32 [E, r] - heads[..., 0, 0] + downstream_room: the net gap from the head car across the
+                        stop line to the last car of the next road - the pair following() leaves out; +inf where either
+                        side has no car"""
+        eng = self.engine
+        if not float(v_min) > 0:
+            raise ValueError("stop_lines: v_min %r is not above 0" % (v_min,))
+        re_ = eng.road_ends(k=k)
+        E, r, m, n, K = eng.E, eng.r, eng.m, eng.n, int(k)
+        if getattr(self, "_ends_idx", None) is None:
+            nxt = self.graph.nexts[:r].astype(np.int64)
+            lengths = eng.archetypes[:, 1] if eng.het else np.array([float(eng.cfg.car_l)], np.float32)
+            self._ends_idx = (torch.as_tensor(np.maximum(nxt, 0)).to(eng.device), torch.as_tensor(nxt >= 0).to(eng.device),
+                              torch.as_tensor(np.asarray(lengths, np.float32)).to(eng.device))
+        nxt, has_next, lengths = self._ends_idx
+        inf = torch.full((), float("inf"), dtype=torch.float32, device=eng.device)
+        heads = re_.heads[:, :r]
+        approach = heads.reshape(E, 4, m, n, K, 2).permute(0, 2, 3, 1, 4, 5)
+        listed = torch.arange(K, device=eng.device) < re_.n_heads[:, :r, None]
+        eta_s = torch.where(listed, heads[..., 0] / heads[..., 1].clamp(min=float(v_min)), inf)
+        some = re_.n_cars > 0
+        row = re_.tail_row.long() if eng.het else torch.zeros_like(re_.n_cars, dtype=torch.int64)
+        length = lengths[torch.where(some, row, torch.zeros_like(row))]
+        entry_room = torch.where(some, re_.tail[..., 0] - length, inf)
+        downstream_room = torch.where(has_next, entry_room[:, nxt], inf)
+        both = some[:, :r] & has_next & some[:, nxt]
+        cross_gap = torch.where(both, heads[:, :, 0, 0] + downstream_room, inf)
+        return VecEnds(*re_, approach, eta_s, entry_room, downstream_room, cross_gap)
 
     def cell_obs(self, n_cells=8, edges=None, v_scale=None, accumulate=False):
         """The discrete traffic state encoding of every env, on the device, with no host synchronisation: every approach
