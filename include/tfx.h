@@ -863,6 +863,46 @@ int tfx_road_ends(tfx_handle h, const tfx_ends_params *p, const tfx_ends_buffers
 /* Test support: the launch geometry tfx_road_ends uses for this handle and k - workgroups, and wavefronts (one per
  * (env, tile) item at a time), like tfx_follow_launch. */
 int tfx_ends_launch(tfx_handle h, int32_t k, int32_t *grid, int32_t *waves);
+/* Car lists on the device: every live car of chosen envs as one flat run, from one read-only launch (k_cars,
+ * csrc/tfx_cars.hpp).  The other road calls reduce a road to a few numbers and tfx_road_ends hands out at most
+ * TFX_MAX_HEADS cars a road; this one hands out all of them, compacted: floating-car data of a few envs per tick, a ragged
+ * (CSR) list for a vehicle-level policy, or chosen envs of a big batch without a whole-batch tfx_export_ring.
+ *
+ * Definition, as a function of the image tfx_export_ring would produce at that moment (on a ring-layout handle: of xv
+ * itself): between two-tick passes, after a clone, between tfx_move_cars and tfx_advance_finished_cars.
+ *   Selection  env_ids holds n_sel env numbers (NULL: selection s is env s, n_sel <= E); repeats are allowed; an id outside
+ *              [0, E) contributes no cars.
+ *   Road filter road_mask is uint8 [R] by road id or NULL; a road whose byte is 0 contributes no cars.
+ *   Counts     count[s][e] = ring_count(leading, lastcar) of road e of env env_ids[s] clamped to 0 .. C-1 - what
+ *              tfx_cars_on_roads returns - and 0 for masked-out roads and for envs that are not shown.
+ *   Offsets    int32 [n_sel * R + 1]: the exclusive prefix sum of the counts in (s, road id) order; offsets[n_sel * R] is
+ *              the total N.  The CALLER computes them (the prefix sum of the tfx_cars_on_roads counts of the chosen envs,
+ *              zeroed where masked or not shown) and passes them in; the library launches no scan.
+ *   Order      car j from the head of (s, e), in ring order (slot wrap(leading + 1 + j); NOT sorted by x), has index
+ *              i = offsets[s * R + e] + j.
+ *   Planes, for every i < min(N, cap):
+ *     xv     float32 [cap][2]  (x, v) of the car, moved bit for bit
+ *     road   int32 [cap]       s * R + e
+ *     row    uint8 [cap]       the car's archetype row; 0 on single-archetype handles
+ *     spawn  float32 [cap]     the car's spawn tick exactly as tfx_export_ring gives it in ring_w; handles with
+ *                              planes == 3 only
+ *   Entries at i >= min(N, cap) are never written.  There is no arithmetic: everything is reproducible byte for byte.
+ * Any plane may be NULL and is then skipped (xv 8-byte aligned).  Memory safety does not depend on the offsets: entry j of
+ * key k = s * R + e is stored only if j < offsets[k + 1] - offsets[k] and offsets[k] + j lies in [0, cap), so offsets that
+ * do not match the counts lose or overlap cars but never send a store outside the planes.
+ *
+ * One launch on `stream`, no host synchronisation; nothing in the handle or in the caller's bound state is written:
+ * captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the launch.  TFX_MEASURE_GRID and
+ * TFX_GRID_CAP cap the launch as they cap the measures'.  TFX_EINVAL: a NULL handle, `out` or `offsets`, n_sel <= 0,
+ * n_sel > E with env_ids NULL, n_sel * R + 1 beyond int32, cap < 0, flags other than 0, `spawn` on a planes == 2 handle;
+ * TFX_ESTATE before tfx_bind_buffers.  cap == 0 is a valid call that launches nothing, as does a refused call.
+ * gym_traffic/devrng.py car_list states the definition in NumPy. */
+typedef struct { float *xv; int32_t *road; uint8_t *row; float *spawn; } tfx_car_list_buffers;  /* any member NULL: skipped */
+int tfx_car_list(tfx_handle h, const int32_t *env_ids /*device, NULL: all*/, int32_t n_sel, const uint8_t *road_mask /*device [R] or NULL*/,
+                 const int32_t *offsets /*device [n_sel*R+1]*/, int32_t cap, const tfx_car_list_buffers *out, int32_t flags, void *stream);
+/* Test support: the launch geometry tfx_car_list uses for this handle and n_sel chosen envs - workgroups, and wavefronts
+ * (one per (selected env, tile) item at a time), like tfx_frames_launch. */
+int tfx_car_list_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

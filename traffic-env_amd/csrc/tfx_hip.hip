@@ -23,6 +23,7 @@
 #include "tfx_cells.hpp"
 #include "tfx_follow.hpp"
 #include "tfx_ends.hpp"
+#include "tfx_cars.hpp"
 #include "tfx_frames.hpp"
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
@@ -1244,6 +1245,49 @@ int tfx_ends_launch(tfx_handle h, int32_t k, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
   if (k < 1 || k > TFX_MAX_HEADS) return fail(TFX_EINVAL, "ends: k %d is outside 1..%d", k, TFX_MAX_HEADS);
   return report_launch(tile_grid(h, true), grid, waves);
+}
+
+// the n_sel of the two car-list calls: at least one selection, and keys s * R + road id that fit an int32
+static int car_list_sel_ok(tfx_handle h, int32_t n_sel) {
+  if (n_sel < 1) return fail(TFX_EINVAL, "car list: n_sel %d is less than 1", n_sel);
+  if ((long long)n_sel * h->d.R + 1 > 0x7fffffffll)
+    return fail(TFX_EINVAL, "car list: %d selections of %d roads do not fit int32 offsets", n_sel, h->d.R);
+  return TFX_OK;
+}
+
+int tfx_car_list(tfx_handle h, const int32_t *env_ids, int32_t n_sel, const uint8_t *road_mask, const int32_t *offsets,
+                 int32_t cap, const tfx_car_list_buffers *out, int32_t flags, void *stream) {
+  if (!out) return fail(TFX_EINVAL, "car list: out is null");
+  if (!offsets) return fail(TFX_EINVAL, "car list: offsets is null");
+  if (cap < 0) return fail(TFX_EINVAL, "car list: cap %d is negative", cap);
+  if (flags) return fail(TFX_EINVAL, "unknown car list flags 0x%x", flags);
+  if (int rc = check_handle(h, false)) return rc;
+  if (int rc = car_list_sel_ok(h, n_sel)) return rc;
+  if (!env_ids && n_sel > h->d.E)
+    return fail(TFX_EINVAL, "car list: n_sel %d is more than the handle's %d envs and env_ids is null", n_sel, h->d.E);
+  if (out->spawn && h->cfg.planes != 3)
+    return fail(TFX_EINVAL, "car list: the handle carries no side plane (planes == 2): spawn ticks are not kept");
+  if (int rc = check_handle(h, true)) return rc;
+  if (cap == 0) return TFX_OK;  // no entry may be written
+  CarsArgs a{};
+  a.env_ids = env_ids;
+  a.road_mask = road_mask;
+  a.offsets = offsets;
+  a.n_sel = n_sel;
+  a.cap = cap;
+  a.xv = reinterpret_cast<f2v *>(out->xv);
+  a.road = out->road;
+  a.row = out->row;
+  a.spawn = out->spawn;
+  if (!a.xv && !a.road && !a.row && !a.spawn) return TFX_OK;  // nothing wanted
+  // k_frames' launch: (selected env, tile) items
+  return launch_query(k_cars, tile_grid(h, true, n_sel), stream, h->d, a);
+}
+
+int tfx_car_list_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (int rc = car_list_sel_ok(h, n_sel)) return rc;
+  return report_launch(tile_grid(h, true, n_sel), grid, waves);
 }
 
 int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *stream) {

@@ -85,6 +85,10 @@ class TfxEndsBuffers(C.Structure):
                 ("tail", C.c_void_p), ("tail_row", C.c_void_p)]
 
 
+class TfxCarListBuffers(C.Structure):
+    _fields_ = [("xv", C.c_void_p), ("road", C.c_void_p), ("row", C.c_void_p), ("spawn", C.c_void_p)]
+
+
 class TfxDemand(C.Structure):
     _fields_ = [("n_profiles", C.c_int32), ("n_segments", C.c_int32), ("seg_ticks", C.c_int32),
                 ("tick_offset", C.c_int32), ("n_cdf", C.c_int32),
@@ -170,6 +174,9 @@ _PROTOS = {
     "tfx_follow_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tfx_road_ends": (C.c_int, [C.c_void_p, C.POINTER(TfxEndsParams), C.POINTER(TfxEndsBuffers), C.c_int32, C.c_void_p]),
     "tfx_ends_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_car_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                               C.POINTER(TfxCarListBuffers), C.c_int32, C.c_void_p]),
+    "tfx_car_list_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

@@ -44,6 +44,11 @@ _FOLLOW_FLOATS = ("gap_sum", "gap_min", "hw_sum", "ttc_min", "drac_max")
 # what road_ends() returns: n_cars, n_heads int32 [E, R]; heads float32 [E, R, k, 2]; head_rows uint8 [E, R, k]; tail
 # float32 [E, R, 2]; tail_row uint8 [E, R] - device tensors by road id (tfx_road_ends, include/tfx.h)
 RoadEnds = collections.namedtuple("RoadEnds", "n_cars n_heads heads head_rows tail tail_row")
+# what car_list() returns: n int32 scalar (the total N) and offsets int32 [n_sel * R + 1], then the planes of max_cars (or N)
+# entries: xv float32 [.., 2], road int32, row uint8, spawn float32 (None on engines without a spawn plane) - device tensors
+# (tfx_car_list, include/tfx.h)
+CarList = collections.namedtuple("CarList", "n offsets xv road row spawn")
+_CAR_PLANES = (("xv", torch.float32, (2,)), ("road", torch.int32, ()), ("row", torch.uint8, ()), ("spawn", torch.float32, ()))
 
 
 def _ptr(t):
@@ -538,6 +543,83 @@ class TfxEngine(object):
         """(workgroups, wavefronts) of the road_ends launch of this engine for k cars a road (tfx_ends_launch; tests)."""
         g, w = C.c_int32(), C.c_int32()
         nat.check(self.lib.tfx_ends_launch(self.h, int(k), C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def car_list(self, env_ids=None, roads=None, max_cars=None, out=None):
+        """Every live car of chosen envs as one flat run, from one read-only launch (tfx_car_list, include/tfx.h;
+        gym_traffic.devrng.car_list states the definition in NumPy): -> CarList(n, offsets, xv, road, row, spawn), device
+        tensors.  env_ids: a list, an array or an int32 device tensor of env numbers (None: every env in order; repeats are
+        fine; an id outside [0, E) contributes no cars); roads: a uint8 / bool mask [R] by road id (None: every road).
+        offsets int32 [n_sel * R + 1] is the exclusive prefix sum of the road counts in (selection s, road id) order - taken
+        here in torch from leading / lastcar with tile_road's clamp - and n = offsets[-1] the total, a device scalar.  Car
+        j from the head of (s, road), in ring order, is entry offsets[s * R + road] + j: xv float32 [.., 2] its (x, v), road
+        int32 its key s * R + road id, row uint8 its archetype row (0 on single-archetype engines), spawn float32 its spawn
+        tick (None on engines without a spawn plane).
+        max_cars = an int: the planes have that length and nothing synchronises with the host; entries from min(n, max_cars)
+        on are not written (fresh tensors are zeroed).  max_cars = None: n is read back once - ONE host synchronisation -
+        and the planes are sized exactly.  out: the caller's (xv, road, row, spawn) of one length, any member None: not
+        computed; then max_cars is that length.  Nothing of the env state is written."""
+        E, R, dev = self.E, self.R, self.device
+        ld, lc = self.leading, self.lastcar
+        count = (lc - ld + (ld > lc).to(torch.int32) * (self.C - 1)).clamp_(0, self.C - 1)
+        if env_ids is None:
+            ids, n_sel = None, E
+        else:
+            if not torch.is_tensor(env_ids):
+                env_ids = torch.as_tensor(np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1)))
+            ids = env_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            n_sel = int(ids.shape[0])
+            if n_sel < 1:
+                raise ValueError("car_list: no env chosen")
+            shown = (ids >= 0) & (ids < E)
+            count = count.index_select(0, torch.where(shown, ids, torch.zeros_like(ids)).long()) * shown[:, None]
+        mask = None
+        if roads is not None:
+            if not torch.is_tensor(roads):
+                roads = torch.as_tensor(np.ascontiguousarray(np.asarray(roads).reshape(-1) != 0))
+            mask = (roads.to(device=dev).reshape(-1) != 0).to(torch.uint8).contiguous()
+            if int(mask.shape[0]) != R:
+                raise ValueError("car_list: roads must have %d entries, one per road id" % R)
+            count = count * mask[None, :]
+        if n_sel * R + 1 > 2 ** 31 - 1:
+            raise ValueError("car_list: %d selections of %d roads do not fit int32 offsets" % (n_sel, R))
+        offsets = torch.zeros((n_sel * R + 1,), dtype=torch.int32, device=dev)
+        torch.cumsum(count.reshape(-1), 0, dtype=torch.int32, out=offsets[1:])
+        n = offsets[-1]
+        if out is not None:
+            planes = list(out)
+            sizes = {int(t.shape[0]) for t in planes if t is not None}
+            if len(planes) != 4 or len(sizes) != 1:
+                raise ValueError("car_list(out=): (xv, road, row, spawn) of one length are needed, any of them None")
+            cap = sizes.pop()
+            if max_cars is not None and int(max_cars) != cap:
+                raise ValueError("car_list(out=): max_cars %d is not the tensors' length %d" % (int(max_cars), cap))
+            for (name, dtype, tail), t in zip(_CAR_PLANES, planes):
+                if t is not None and (t.dtype != dtype or tuple(t.shape) != (cap,) + tail or not t.is_contiguous()
+                                      or not t.is_cuda):
+                    raise ValueError("car_list(out=): %s must be a contiguous %s %s device tensor"
+                                     % (name, dtype, [cap] + list(tail)))
+            if planes[3] is not None and self.P != 3:
+                raise ValueError("car_list(out=): the engine keeps no spawn ticks (planes == 2)")
+        else:
+            cap = int(n) if max_cars is None else int(max_cars)      # int(n): the one host synchronisation
+            if cap < 0:
+                raise ValueError("car_list: max_cars %d is negative" % cap)
+            planes = [torch.zeros((cap,) + tail, dtype=dtype, device=dev) if (name != "spawn" or self.P == 3) else None
+                      for name, dtype, tail in _CAR_PLANES]
+        if cap > 2 ** 31 - 1:
+            raise ValueError("car_list: %d entries do not fit int32 offsets" % cap)
+        b = nat.TfxCarListBuffers(*[_ptr(t) for t in planes])
+        with torch.cuda.device(dev):
+            nat.check(self.lib.tfx_car_list(self.h, _ptr(ids), n_sel, _ptr(mask), _ptr(offsets), cap, C.byref(b), 0,
+                                            self._stream()))
+        return CarList(n, offsets, *planes)
+
+    def car_list_launch(self, n_sel):
+        """(workgroups, wavefronts) of the car_list launch of this engine for n_sel chosen envs (tfx_car_list_launch;
+        tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_car_list_launch(self.h, int(n_sel), C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
 
     def car_ages(self, accumulate=False, out=None):

@@ -295,6 +295,67 @@ def road_ends(x, v, leading, lastcar, C, length, k, pad_dist, pad_v, pad_tail_x,
             tail_row.reshape(shape))
 
 
+CAR_LIST_FIELDS = ("n", "offsets", "xv", "road", "row", "spawn")
+
+
+def car_list(x, v, w, arch, leading, lastcar, C, env_ids=None, road_mask=None, cap=None, out=None):
+    """The definition of tfx_car_list (include/tfx.h) in NumPy, over ring planes: x, v float32 [E, R, C] by ring slot (what
+    tfx_export_ring produces), w float32 [E, R, C] the spawn ticks (None on handles with planes == 2: no spawn plane),
+    arch uint8 [E, R, C] the archetype row of every ring slot on heterogeneous handles (None: every row is 0), leading /
+    lastcar int [E, R].  env_ids: n_sel env numbers (None: every env in order; repeats allowed; an id outside [0, E)
+    contributes no cars); road_mask uint8 [R] or None (a road with mask 0 contributes no cars); cap: entries the planes
+    hold (None: exactly N).  -> a tuple in the order of CAR_LIST_FIELDS: n (the total N, an int), offsets int32
+    [n_sel * R + 1], xv float32 [cap, 2], road int32 [cap], row uint8 [cap], spawn float32 [cap] or None.
+    count[s][road] is the ring count clamped to 0 .. C-1, 0 for masked-out roads and envs that are not shown; offsets is
+    its exclusive prefix sum in (s, road id) order.  Car j from the head, in ring order (slot wrap(leading + 1 + j), never
+    sorted by x), of (s, road) has index i = offsets[s * R + road] + j; for i < min(N, cap): xv[i] = (x, v), road[i] =
+    s * R + road, row[i] its archetype row, spawn[i] its spawn tick - all moved bit for bit.  Entries at i >= min(N, cap)
+    are never written: they keep what `out` (xv, road, row, spawn - any None) held, zeros where it gave nothing."""
+    C = int(C)
+    x = np.asarray(x, np.float32)
+    v = np.asarray(v, np.float32)
+    E, R = x.shape[0], x.shape[1]
+    ld = np.asarray(leading, np.int64).reshape(E, R)
+    lc = np.asarray(lastcar, np.int64).reshape(E, R)
+    n = np.clip(lc - ld + np.where(ld > lc, C - 1, 0), 0, C - 1)
+    ids = np.arange(E, dtype=np.int64) if env_ids is None else np.asarray(env_ids, np.int64).reshape(-1)
+    shown = (ids >= 0) & (ids < E)
+    env = np.where(shown, ids, 0)
+    count = n[env] * shown[:, None]
+    if road_mask is not None:
+        count = count * (np.asarray(road_mask).reshape(R) != 0)[None, :]
+    n_sel = len(ids)
+    offsets = np.zeros(n_sel * R + 1, np.int64)
+    np.cumsum(count.reshape(-1), out=offsets[1:])
+    N = int(offsets[-1])
+    cap = N if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("car_list: cap %d is negative" % cap)
+    planes = dict(xv=(np.float32, (cap, 2)), road=(np.int32, (cap,)), row=(np.uint8, (cap,)), spawn=(np.float32, (cap,)))
+    given = dict(zip(("xv", "road", "row", "spawn"), out if out is not None else (None,) * 4))
+    res = {}
+    for name, (dtype, shape) in planes.items():
+        a = given[name]
+        res[name] = np.zeros(shape, dtype) if a is None else np.array(a, dtype).reshape(shape)
+    if w is None:
+        res["spawn"] = None
+    top = min(N, cap)
+    # every listed car: its key, its rank from the head, its ring slot
+    key = np.repeat(np.arange(n_sel * R), count.reshape(-1))[:top]
+    rank = np.arange(top) - offsets[key]
+    sel, rd = key // R, key % R
+    e = env[sel]
+    slot = ld[e, rd] + 1 + rank
+    slot = np.where(slot > C - 1, slot - (C - 1), slot)
+    res["xv"][:top, 0] = x[e, rd, slot]
+    res["xv"][:top, 1] = v[e, rd, slot]
+    res["road"][:top] = key
+    res["row"][:top] = 0 if arch is None else np.asarray(arch, np.uint8)[e, rd, slot]
+    if w is not None:
+        res["spawn"][:top] = np.asarray(w, np.float32)[e, rd, slot]
+    return (N, offsets.astype(np.int32), res["xv"], res["road"], res["row"], res["spawn"])
+
+
 def car_ages(w, leading, lastcar, C, now, het=False):
     """The definition of tfx_car_ages (include/tfx.h) in NumPy, over the ring plane w float32 [..., R, C] of spawn ticks
     by ring slot (what tfx_export_ring produces; heterogeneous handles: the spawn tick modulo 2^24), leading / lastcar

@@ -62,6 +62,8 @@ VecFollowing = collections.namedtuple("VecFollowing", "n_cars n_pairs n_joined n
 # what TrafficVecEnv.stop_lines() returns: the engine's six road-end tensors and the views derived from them
 VecEnds = collections.namedtuple("VecEnds", "n_cars n_heads heads head_rows tail tail_row approach eta_s entry_room "
                                             "downstream_room cross_gap")
+# what TrafficVecEnv.cars() returns: the engine's car list and the per-car views derived from it
+VecCars = collections.namedtuple("VecCars", "n offsets xv road row spawn sel road_id rank dist age_ticks valid")
 # what TrafficVecEnv.cell_obs() returns: the engine's two per-cell tensors and the image a convolutional policy reads
 VecCells = collections.namedtuple("VecCells", "n_cars speed_sum image")
 # what TrafficVecEnv.travel_times() returns: per-env travel-time figures, finished trips and cars still on the map
@@ -577,6 +579,57 @@ class TrafficVecEnv(object):
         both = some[:, :r] & has_next & some[:, nxt]
         cross_gap = torch.where(both, heads[:, :, 0, 0] + downstream_room, inf)
         return VecEnds(*re_, approach, eta_s, entry_room, downstream_room, cross_gap)
+
+    def cars(self, envs=None, roads=None, max_cars=None):
+        """Every car of chosen envs as one flat, ragged (CSR) list on the device: floating-car data for logging, the
+        input of a vehicle-level policy, or a look into a few envs of a big batch - one read-only launch that stores the
+        live cars compacted (TfxEngine.car_list / tfx_car_list, include/tfx.h) plus a few torch expressions.  envs: a
+        list, an array or an int32 device tensor of env numbers (None: every env; repeats are fine; an id outside [0, E)
+        has no cars); roads: a uint8 / bool mask [R] by road id, e.g. arterial(...) (None: every road); max_cars: the
+        length of the per-car tensors - with an int nothing synchronises with the host, with None the total is read
+        back once and the tensors are sized exactly.  -> VecCars:
+            n           int32 scalar - the cars of the chosen envs and roads (may exceed max_cars: then the list is cut)
+            offsets     int32 [n_sel * R + 1] - cars of (selection s, road) are entries offsets[s * R + road] ..
+                        offsets[s * R + road + 1], head first, in ring order
+            xv          float32 [L, 2] (x, v); road int32 [L] the key s * R + road id; row uint8 [L] the archetype row;
+                        spawn float32 [L] the spawn tick, None unless the env is validate or heterogeneous
+            sel, road_id int64 [L] - road // R and road % R; rank int64 [L] - the car's place from the head of its road
+            dist        float32 [L] - length - x, the distance to the stop line
+            age_ticks   int32 [L] - ticks since the car was spawned (TfxEngine.car_ages' rule), None where spawn is
+            valid       bool [L] - arange(L) < n: entries that hold a car; the others are zero"""
+        eng = self.engine
+        cl = eng.car_list(env_ids=envs, roads=roads, max_cars=max_cars)
+        L, R = int(cl.xv.shape[0]), eng.R
+        at = torch.arange(L, device=eng.device)
+        valid = at < cl.n
+        key = cl.road.long()
+        sel, road_id = key // R, key % R
+        rank = torch.where(valid, at - cl.offsets[:-1][key].long(), torch.zeros_like(at))
+        dist = float(eng.cfg.length) - cl.xv[:, 0]
+        age = None
+        if cl.spawn is not None:
+            if eng.het:
+                age = (int(eng.tick) - cl.spawn.to(torch.int64)).bitwise_and(0xFFFFFF).to(torch.int32)
+            else:
+                age = (torch.full((), float(int(eng.tick)), dtype=torch.float32, device=eng.device) - cl.spawn).to(torch.int32)
+            age = torch.where(valid, age, torch.zeros_like(age))
+        return VecCars(*cl, sel, road_id, rank, dist, age, valid)
+
+    def arterial(self, row_or_col, direction):
+        """uint8 [R] road mask of one arterial: the chain of roads a car of `direction` (0 eastbound, 1 westbound - along
+        row `row_or_col`; 2 towards higher rows, 3 towards lower rows - along column `row_or_col`) drives through, from
+        its entry road to the exit road, found by following the GridRoad `nexts` table.  For cars(roads=...)."""
+        g = self.graph
+        m, n, v = g.m, g.n, g.m * g.n
+        i, d = int(row_or_col), int(direction)
+        if d not in (0, 1, 2, 3) or not 0 <= i < (m if d < 2 else n):
+            raise ValueError("arterial: direction %r / index %r is not on the %d x %d grid" % (direction, row_or_col, m, n))
+        road = (i * n, v + i * n + n - 1, 2 * v + i, 3 * v + (m - 1) * n + i)[d]
+        mask = np.zeros(g.roads, np.uint8)
+        while road >= 0:
+            mask[road] = 1
+            road = int(g.nexts[road])
+        return mask
 
     def cell_obs(self, n_cells=8, edges=None, v_scale=None, accumulate=False):
         """The discrete traffic state encoding of every env, on the device, with no host synchronisation: every approach
