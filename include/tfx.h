@@ -903,6 +903,60 @@ int tfx_car_list(tfx_handle h, const int32_t *env_ids /*device, NULL: all*/, int
 /* Test support: the launch geometry tfx_car_list uses for this handle and n_sel chosen envs - workgroups, and wavefronts
  * (one per (selected env, tile) item at a time), like tfx_frames_launch. */
 int tfx_car_list_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves);
+/* Car lists back in: the cars of chosen envs written from one flat run, in one launch (k_put, csrc/tfx_put.hpp) - the
+ * inverse of tfx_car_list.  Edit a list and write it back, restart chosen envs from a library of lists, move envs between
+ * batches of another E or capacity: a list is plain data, a handle is not.
+ *
+ * Definition, on the image tfx_export_ring would produce afterwards (on a ring-layout handle: xv itself), for every
+ * selection s whose env = env_ids[s] lies in [0, E) (NULL: selection s is env s, n_sel <= E) and every road e whose
+ * road_mask byte is non-zero (NULL: every road), with key = s * R + e:
+ *   Run        base = offsets[key], run = max(0, offsets[key + 1] - base); the entries offered are those of
+ *              [base, base + run) that lie in [0, cap): first = max(base, 0), fit = max(0, min(base + run, cap) - first).
+ *   Count      the road afterwards holds n = min(fit, C - 2) cars - a ring of C - 1 slots, one of them the leader's, holds
+ *              no more (with C - 1 the ring words would read as an empty road); on the transposed layout also n <= the
+ *              tile's rows.  tfx_cars_on_roads then returns n.
+ *   Cars       car j < n from the head is entry first + j of the planes: (x, v) moved bit for bit; the side word built as
+ *              tfx_import_ring builds it from (spawn, row) - on planes == 2 handles spawn is ignored - with spawn_shift
+ *              added to every spawn tick as tfx_clone_envs adds the difference of two clocks (a list recorded at another
+ *              clock is rebased; on heterogeneous handles modulo 2^24).
+ *   Ring words leading' = leading[key] where that is a ring index of this handle (1 .. C-1), otherwise - or with
+ *              `leading` NULL - the road's current one; lastcar' = the slot of car n - 1 (leading' + n under the ring's
+ *              wrap), leading' itself when n == 0.  Slot leading' shows lead_x[key] (NULL: +INFINITY, what a reset writes).
+ *              The value is for the image only: the next tick's light update rewrites it on every road that has a light,
+ *              and on exit roads the model's leader is +INFINITY always - pass that there.
+ *   Lost       the first n cars offered are taken; run - n is added to *lost (device, may be NULL) with one atomicAdd per
+ *              road that loses cars, and nothing else happens.
+ *   Untouched  roads that are masked out, envs that are not selected and selections whose id lies outside [0, E) keep their
+ *              cars, ring words and caches bit for bit.  Slots or rows of a written road that hold no car afterwards are
+ *              unspecified.
+ *   Caches     the launch writes every per-road word tfx_import_ring followed by tfx_refresh would leave for the road - the
+ *              row offset of the two-tick pass (0), the leader's x, the tail caches with tfx_refresh's values, empty roads
+ *              and the ring layout included - so no tfx_refresh is needed.  Everything else the handle keeps (records,
+ *              stamps, graphs) is left alone: by "What the next call depends on" above such residue never changes a result.
+ * env_ids must be distinct.  With repeats the launch is still memory-safe and the env's ring words stay ring indices, but
+ * which of the offered runs a road's words and car rows come from is unspecified.  Memory safety does not depend on the
+ * offsets: entry i of a plane is read only if 0 <= i < cap, and stores go to the selected envs' own columns and words only.
+ *
+ * One launch on `stream`, no host synchronisation; no pointer changes, so captured step / agent-step graphs stay valid;
+ * tfx_debug_fail_after does not count the launch and TFX_GRID_CAP caps it.  The call belongs between whole ticks: between
+ * tfx_move_cars and tfx_advance_finished_cars the outbox of a written road is stale and the advance would hand on cars
+ * that are no longer there - the handle does not track that state, so this is the caller's rule, not an error code.
+ * TFX_EINVAL: a NULL handle, `in`, `in->xv` or `offsets`, n_sel <= 0, n_sel > E with env_ids NULL, n_sel * R + 1 beyond
+ * int32, cap < 0, flags other than 0; TFX_ESTATE before tfx_bind_buffers.  cap == 0 is valid and empties the selected
+ * roads.  gym_traffic/devrng.py put_cars states the definition in NumPy. */
+typedef struct {
+  const float   *xv;      /* [cap][2] (x, v); required */
+  const uint8_t *row;     /* [cap] archetype row; NULL: row 0 */
+  const float   *spawn;   /* [cap] spawn tick as tfx_car_list / ring_w give it; NULL: 0 */
+  const int32_t *leading; /* [n_sel*R] new `leading` per (selection, road); NULL or a value that is no valid ring index of this handle: the road keeps its current one */
+  const float   *lead_x;  /* [n_sel*R] the x the image shows in slot `leading`; NULL: +INFINITY (what a reset writes) */
+} tfx_put_buffers;
+int tfx_put_cars(tfx_handle h, const int32_t *env_ids /*device, NULL: selection s is env s*/, int32_t n_sel,
+                 const uint8_t *road_mask /*device [R] or NULL*/, const int32_t *offsets /*device [n_sel*R+1]*/,
+                 int32_t cap, const tfx_put_buffers *in, int32_t spawn_shift, uint64_t *lost /*device, may be NULL*/,
+                 int32_t flags, void *stream);
+/* Test support: the launch geometry tfx_put_cars uses for this handle and n_sel chosen envs, like tfx_car_list_launch. */
+int tfx_put_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

@@ -24,6 +24,7 @@
 #include "tfx_follow.hpp"
 #include "tfx_ends.hpp"
 #include "tfx_cars.hpp"
+#include "tfx_put.hpp"
 #include "tfx_frames.hpp"
 #include "tfx_clone.hpp"
 #include "tfx_measure.hpp"
@@ -1288,6 +1289,49 @@ int tfx_car_list_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *wav
   if (int rc = check_handle(h, false)) return rc;
   if (int rc = car_list_sel_ok(h, n_sel)) return rc;
   return report_launch(tile_grid(h, true, n_sel), grid, waves);
+}
+
+int tfx_put_cars(tfx_handle h, const int32_t *env_ids, int32_t n_sel, const uint8_t *road_mask, const int32_t *offsets,
+                 int32_t cap, const tfx_put_buffers *in, int32_t spawn_shift, uint64_t *lost, int32_t flags, void *stream) {
+  if (!in) return fail(TFX_EINVAL, "put cars: in is null");
+  if (!in->xv) return fail(TFX_EINVAL, "put cars: in->xv is null");
+  if (!offsets) return fail(TFX_EINVAL, "put cars: offsets is null");
+  if (cap < 0) return fail(TFX_EINVAL, "put cars: cap %d is negative", cap);
+  if (flags) return fail(TFX_EINVAL, "unknown put cars flags 0x%x", flags);
+  if (int rc = check_handle(h, false)) return rc;
+  if (int rc = car_list_sel_ok(h, n_sel)) return rc;
+  if (!env_ids && n_sel > h->d.E)
+    return fail(TFX_EINVAL, "put cars: n_sel %d is more than the handle's %d envs and env_ids is null", n_sel, h->d.E);
+  if (int rc = check_handle(h, true)) return rc;
+  PutArgs a{};
+  a.env_ids = env_ids;
+  a.road_mask = road_mask;
+  a.offsets = offsets;
+  a.n_sel = n_sel;
+  a.cap = cap;  // (0: every selected road is emptied)
+  a.xv = reinterpret_cast<const f2v *>(in->xv);
+  a.row = in->row;
+  a.spawn = h->cfg.planes == 3 ? in->spawn : nullptr;
+  a.leading = in->leading;
+  a.lead_x = in->lead_x;
+  a.spawn_shift = spawn_shift;
+  a.lost = reinterpret_cast<unsigned long long *>(lost);
+  // k_cars' items: (selected env, tile) pairs.  Not counted by tfx_debug_fail_after; no pointer of the handle changes, so
+  // captured graphs stay valid
+  const long grid = tile_grid(h, false, n_sel);
+  // Non-temporal row stores where the mover uses them (pick_move_t: the handle's cars do not fit the Infinity Cache, so
+  // the next tick finds none of them there anyway): 1113 -> 1029 us for xv of all 4096 envs of cfg2, 75.9 -> 65.8 us for
+  // 256 envs, no difference below (profiles/put_cars.txt).  TFX_PUT_NT=0 / 1, read per call, forces a form
+  // (tools/time_put_cars.py measures both on one handle).
+  const char *ntv = getenv("TFX_PUT_NT");
+  const bool nt = ntv ? atoi(ntv) != 0 : (size_t)h->d.E * env_car_pairs(h->d) * sizeof(float2) > ((size_t)448 << 20);
+  return nt ? launch_query(k_put<true>, grid, stream, h->d, a) : launch_query(k_put<false>, grid, stream, h->d, a);
+}
+
+int tfx_put_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (int rc = car_list_sel_ok(h, n_sel)) return rc;
+  return report_launch(tile_grid(h, false, n_sel), grid, waves);
 }
 
 int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *stream) {

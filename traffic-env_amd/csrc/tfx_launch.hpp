@@ -158,8 +158,8 @@ long item_grid(const tfx_handle_s *h, long items, bool measure = false) {
 }
 
 // ... of the kernels whose items are (env, tile) pairs: k_clone, and in the measure form k_measure, k_ages and k_cells.
-// n_frames > 0: k_frames' launch - its items are (frame, tile) pairs of the frames drawn - and k_cars', whose items are
-// (selected env, tile) pairs
+// n_frames > 0: k_frames' launch - its items are (frame, tile) pairs of the frames drawn - and k_cars' and k_put's, whose
+// items are (selected env, tile) pairs
 long tile_grid(const tfx_handle_s *h, bool measure = false, long n_frames = 0) {
   return item_grid(h, (n_frames > 0 ? n_frames : (long)h->d.E) * h->d.G, measure);
 }

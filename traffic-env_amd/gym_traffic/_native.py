@@ -89,6 +89,11 @@ class TfxCarListBuffers(C.Structure):
     _fields_ = [("xv", C.c_void_p), ("road", C.c_void_p), ("row", C.c_void_p), ("spawn", C.c_void_p)]
 
 
+class TfxPutBuffers(C.Structure):
+    _fields_ = [("xv", C.c_void_p), ("row", C.c_void_p), ("spawn", C.c_void_p), ("leading", C.c_void_p),
+                ("lead_x", C.c_void_p)]
+
+
 class TfxDemand(C.Structure):
     _fields_ = [("n_profiles", C.c_int32), ("n_segments", C.c_int32), ("seg_ticks", C.c_int32),
                 ("tick_offset", C.c_int32), ("n_cdf", C.c_int32),
@@ -177,6 +182,9 @@ _PROTOS = {
     "tfx_car_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                C.POINTER(TfxCarListBuffers), C.c_int32, C.c_void_p]),
     "tfx_car_list_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_put_cars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                               C.POINTER(TfxPutBuffers), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "tfx_put_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

@@ -622,6 +622,158 @@ class TfxEngine(object):
         nat.check(self.lib.tfx_car_list_launch(self.h, int(n_sel), C.byref(g), C.byref(w)))
         return int(g.value), int(w.value)
 
+    def _dev(self, a, dtype, np_dtype, shape, what):
+        """a caller's tensor or array-like as a contiguous device tensor of this dtype and shape (None stays None)"""
+        if a is None:
+            return None
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.ascontiguousarray(np.asarray(a, np_dtype)))
+        a = a.to(device=self.device, dtype=dtype).contiguous()
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("put_cars: %s must have shape %s, not %s" % (what, list(shape), list(a.shape)))
+        return a
+
+    def put_cars(self, offsets, xv=None, row=None, spawn=None, env_ids=None, roads=None, leading=None, lead_x=None,
+                 spawn_shift=0, count_lost=False):
+        """The cars of chosen envs written from one flat run, in one launch and with no host synchronisation - the inverse
+        of car_list (tfx_put_cars, include/tfx.h; gym_traffic.devrng.put_cars states the definition in NumPy).  offsets
+        int32 [n_sel * R + 1], xv float32 [cap, 2], row uint8 [cap] (None: row 0), spawn float32 [cap] (None: tick 0; ignored
+        by engines without a spawn plane) are a list as car_list returns it - device tensors or array-likes; a CarList may
+        be passed whole as the first argument.  Road `road` of env env_ids[s] (None: env s) then holds the cars at
+        offsets[s * R + road] .. offsets[s * R + road + 1], head first, at most C - 2 of them and none from outside [0, cap).
+        roads: a uint8 / bool mask [R] (None: every road) - the others keep their cars; leading int32 [n_sel, R]: the roads'
+        new `leading` (None or no ring index: unchanged); lead_x float32 [n_sel, R]: the x the leader's slot shows (None:
+        +inf, as after a reset); spawn_shift: added to every spawn tick (a list taken at another clock).  env_ids must be
+        distinct: a host-side list with repeats raises.  count_lost: cars that did not fit are added to the counter
+        put_lost() reads.  Nothing else of the engine's state changes and no refresh() is needed."""
+        if isinstance(offsets, CarList):
+            cl = offsets
+            offsets, xv = cl.offsets, cl.xv if xv is None else xv
+            row = cl.row if row is None else row
+            spawn = cl.spawn if spawn is None else spawn
+        if xv is None:
+            raise ValueError("put_cars: xv is needed")
+        R, dev = self.R, self.device
+        if not torch.is_tensor(offsets):
+            offsets = torch.as_tensor(np.ascontiguousarray(np.asarray(offsets, np.int32).reshape(-1)))
+        offsets = offsets.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        n_keys = int(offsets.shape[0]) - 1
+        if n_keys < R or n_keys % R:
+            raise ValueError("put_cars: offsets must hold n_sel * %d + 1 entries, not %d" % (R, n_keys + 1))
+        n_sel = n_keys // R
+        ids = None
+        if env_ids is not None:
+            if not torch.is_tensor(env_ids):
+                host_ids = np.asarray(env_ids, np.int64).reshape(-1)
+                shown = host_ids[(host_ids >= 0) & (host_ids < self.E)]
+                if len(np.unique(shown)) != len(shown):
+                    raise ValueError("put_cars: env_ids must be distinct")
+                env_ids = torch.as_tensor(np.ascontiguousarray(host_ids.astype(np.int32)))
+            ids = env_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            if int(ids.shape[0]) != n_sel:
+                raise ValueError("put_cars: %d env ids for offsets of %d selections" % (int(ids.shape[0]), n_sel))
+        elif n_sel > self.E:
+            raise ValueError("put_cars: offsets of %d selections for %d envs" % (n_sel, self.E))
+        mask = None
+        if roads is not None:
+            if not torch.is_tensor(roads):
+                roads = torch.as_tensor(np.ascontiguousarray(np.asarray(roads).reshape(-1) != 0))
+            mask = (roads.to(device=dev).reshape(-1) != 0).to(torch.uint8).contiguous()
+            if int(mask.shape[0]) != R:
+                raise ValueError("put_cars: roads must have %d entries, one per road id" % R)
+        if not torch.is_tensor(xv):
+            xv = torch.as_tensor(np.ascontiguousarray(np.asarray(xv, np.float32).reshape(-1, 2)))
+        xv = xv.to(device=dev, dtype=torch.float32).contiguous()
+        cap = int(xv.shape[0])
+        if xv.dim() != 2 or xv.shape[1] != 2 or cap > 2 ** 31 - 1:
+            raise ValueError("put_cars: xv must be [cap, 2] with cap below 2^31")
+        row = self._dev(row, torch.uint8, np.uint8, (cap,), "row")
+        spawn = self._dev(spawn, torch.float32, np.float32, (cap,), "spawn") if self.P == 3 else None
+        leading = self._dev(None if leading is None else leading.reshape(-1) if torch.is_tensor(leading)
+                            else np.asarray(leading).reshape(-1), torch.int32, np.int32, (n_keys,), "leading")
+        lead_x = self._dev(None if lead_x is None else lead_x.reshape(-1) if torch.is_tensor(lead_x)
+                           else np.asarray(lead_x).reshape(-1), torch.float32, np.float32, (n_keys,), "lead_x")
+        if count_lost and getattr(self, "_put_lost", None) is None:
+            self._put_lost = torch.zeros((1,), dtype=torch.int64, device=dev)
+        if cap == 0:
+            xv = torch.zeros((1, 2), dtype=torch.float32, device=dev)      # (a pointer to pass: no entry of it is read)
+        b = nat.TfxPutBuffers(_ptr(xv), _ptr(row), _ptr(spawn), _ptr(leading), _ptr(lead_x))
+        self._epoch += 1
+        with torch.cuda.device(dev):
+            nat.check(self.lib.tfx_put_cars(self.h, _ptr(ids), n_sel, _ptr(mask), _ptr(offsets), cap, C.byref(b),
+                                            int(spawn_shift), _ptr(self._put_lost) if count_lost else None, 0,
+                                            self._stream()))
+        # (the launch reads these after the call returns: the caching allocator hands a freed block out again to work on
+        # the same stream only, which is ordered behind the launch)
+        self._put_keep = (ids, mask, offsets, xv, row, spawn, leading, lead_x)
+
+    def put_lost(self):
+        """Cars earlier put_cars(count_lost=True) calls could not place - runs longer than a road holds or cut by the
+        planes' length - since the last call of this: reads and clears the device counter; synchronises."""
+        t = getattr(self, "_put_lost", None)
+        if t is None:
+            return 0
+        n = int(t.item())
+        t.zero_()
+        return n
+
+    # the bound per-env rows pack_envs gathers by index
+    _PACK_ROWS = ("obs", "rewards", "waiting", "passed_dst", "done_tick", "done")
+
+    def pack_envs(self, envs):
+        """Everything a caller can see of the chosen envs as a plain dict of device tensors: the car list (offsets, xv,
+        row, spawn) with the roads' `leading`, the rows of obs, rewards, waiting, passed_dst, done_tick and done, with a
+        trip log its rows and n_trips, and the clock (`tick`), grid and capacity it was taken at.  One car_list launch plus
+        torch indexing; the total number of cars is read back once.  The arrival stream's position, the greedy
+        controller's held action and the episode accounting are not in it (they travel through clone_envs only)."""
+        if not torch.is_tensor(envs):
+            envs = torch.as_tensor(np.ascontiguousarray(np.asarray(envs, np.int64).reshape(-1)))
+        idx = envs.to(device=self.device, dtype=torch.int64).reshape(-1)
+        cl = self.car_list(env_ids=idx.to(torch.int32))
+        packed = dict(offsets=cl.offsets, xv=cl.xv, row=cl.row, spawn=cl.spawn, leading=self.leading[idx].clone(),
+                      tick=int(self.tick), grid=(self.m, self.n, float(self.cfg.length)), capacity=self.C)
+        for k in self._PACK_ROWS:
+            packed[k] = getattr(self, k)[idx].clone()
+        if self.n_trips is not None:
+            packed["n_trips"] = self.n_trips[idx].clone()
+            packed["trip_times"] = self.trip_times[idx].clone()
+        return packed
+
+    def unpack_envs(self, envs, packed):
+        """envs[s] of this engine receives selection s of what pack_envs returned - of this engine or of another one on the
+        same grid, whatever its E and capacity: one put_cars launch plus torch index writes, no host synchronisation.
+        Cars that do not fit are counted in put_lost(); spawn ticks and the done_tick stamp are rebased by the difference
+        of the two clocks; the trip log is cut to this engine's trip_cap.  envs must be distinct.  -> the ids as an int64
+        device tensor."""
+        grid = (self.m, self.n, float(self.cfg.length))
+        if tuple(packed["grid"]) != grid:
+            raise ValueError("unpack_envs: packed on grid %r, this engine is %r" % (tuple(packed["grid"]), grid))
+        host_ids = None if torch.is_tensor(envs) else np.asarray(envs, np.int64).reshape(-1)
+        idx = (envs if host_ids is None else torch.as_tensor(np.ascontiguousarray(host_ids))).to(
+            device=self.device, dtype=torch.int64).reshape(-1)
+        if int(idx.shape[0]) != int(packed["leading"].shape[0]):
+            raise ValueError("unpack_envs: %d envs for %d packed ones" % (int(idx.shape[0]), int(packed["leading"].shape[0])))
+        dt = int(self.tick) - int(packed["tick"])
+        self.put_cars(packed["offsets"], packed["xv"], row=packed["row"], spawn=packed["spawn"],
+                      env_ids=host_ids if host_ids is not None else idx.to(torch.int32), leading=packed["leading"],
+                      spawn_shift=dt, count_lost=True)
+        for k in self._PACK_ROWS:
+            src = packed[k].to(self.device)
+            if k == "done_tick":
+                src = torch.where(src != 0, src + dt, src)      # (a stamp: tick + 1 of a past tick, 0 = never)
+            getattr(self, k)[idx] = src
+        if self.n_trips is not None and "n_trips" in packed:
+            n = min(self.trip_cap, int(packed["trip_times"].shape[1]))
+            self.n_trips[idx] = packed["n_trips"].to(self.device)
+            self.trip_times[idx, :n] = packed["trip_times"].to(self.device)[:, :n]
+        return idx
+
+    def put_launch(self, n_sel):
+        """(workgroups, wavefronts) of the put_cars launch of this engine for n_sel chosen envs (tfx_put_launch; tests)."""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(self.lib.tfx_put_launch(self.h, int(n_sel), C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
     def car_ages(self, accumulate=False, out=None):
         """How long every live car has been on the map, per road, from one read-only launch over the side plane
         (tfx_car_ages, include/tfx.h; gym_traffic.devrng.car_ages states the definition in NumPy): -> CarAges(n_cars
@@ -789,7 +941,8 @@ class TfxEngine(object):
 
     def refresh(self, cars=None):
         """After writing xv / leading / lastcar from outside: push the ring-layout staging copy to
-        the device layout (transposed handles) and rebuild the tail cache.
+        the device layout (transposed handles) and rebuild the tail cache.  This route copies every ring slot of the
+        whole batch; put_cars() writes the cars of chosen envs from a flat list and needs no refresh().
 
         The staging copy mirrors the device only until the cars move again.  A caller that kept a
         reference to `xv` / `x` / `v` / `w` across a step and wrote into it holds a STALE image: pushing

@@ -356,6 +356,65 @@ def car_list(x, v, w, arch, leading, lastcar, C, env_ids=None, road_mask=None, c
     return (N, offsets.astype(np.int32), res["xv"], res["road"], res["row"], res["spawn"])
 
 
+def put_cars(x, v, w, arch, leading, lastcar, C, offsets, xv, row, spawn, env_ids=None, road_mask=None, new_leading=None,
+             lead_x=None, spawn_shift=0, het=False):
+    """The definition of tfx_put_cars (include/tfx.h) in NumPy, over ring planes - the inverse of car_list where nothing is
+    clipped: x, v float32 [E, R, C] by ring slot, w float32 [E, R, C] the spawn ticks (None on handles with planes == 2),
+    arch uint8 [E, R, C] (None: no rows kept), leading / lastcar int [E, R] are the image before the call; offsets int
+    [n_sel * R + 1], xv float32 [cap, 2], row uint8 [cap] or None (row 0), spawn float32 [cap] or None (tick 0) the list;
+    env_ids n_sel env numbers (None: selection s is env s; an id outside [0, E) writes nothing); road_mask uint8 [R] or None;
+    new_leading int [n_sel * R] or None, lead_x float32 [n_sel * R] or None (+inf).  -> (x', v', w', arch', leading',
+    lastcar', lost): copies; slots the call leaves unspecified keep what they held.
+    For key = s * R + road: base = offsets[key], run = max(0, offsets[key + 1] - base), first = max(base, 0), fit =
+    max(0, min(base + run, cap) - first); the road then holds n = min(fit, C - 2) cars, car j in slot wrap(leading' + 1 + j)
+    from entry first + j; leading' = new_leading[key] where that lies in 1 .. C-1, otherwise the road's own; lastcar' the
+    slot of car n - 1, leading' when n == 0; slot leading' shows lead_x[key]; lost sums run - n.  The spawn tick becomes
+    spawn + spawn_shift (heterogeneous handles, het: int(spawn) + spawn_shift modulo 2^24, the row modulo 64)."""
+    C = int(C)
+    x, v = np.array(x, np.float32), np.array(v, np.float32)
+    E, R = x.shape[0], x.shape[1]
+    w = None if w is None else np.array(w, np.float32)
+    arch = None if arch is None else np.array(arch, np.uint8)
+    ld = np.array(leading, np.int64).reshape(E, R)
+    lc = np.array(lastcar, np.int64).reshape(E, R)
+    xv = np.asarray(xv, np.float32).reshape(-1, 2)
+    cap = len(xv)
+    off = np.asarray(offsets, np.int64).reshape(-1)
+    ids = np.arange((len(off) - 1) // R, dtype=np.int64) if env_ids is None else np.asarray(env_ids, np.int64).reshape(-1)
+    mask = np.ones(R, bool) if road_mask is None else np.asarray(road_mask).reshape(R) != 0
+    shift = int(spawn_shift)
+    lost = 0
+    for s, env in enumerate(ids):
+        if not 0 <= env < E:
+            continue
+        for rd in np.flatnonzero(mask):
+            key = s * R + rd
+            base = int(off[key])
+            run = max(0, int(off[key + 1]) - base)
+            first = max(base, 0)
+            n = min(max(0, min(base + run, cap) - first), C - 2)
+            lost += run - n
+            l = ld[env, rd]
+            if new_leading is not None and 1 <= int(np.asarray(new_leading).reshape(-1)[key]) <= C - 1:
+                l = int(np.asarray(new_leading).reshape(-1)[key])
+            slot = (l + np.arange(n)) % (C - 1) + 1
+            take = first + np.arange(n)
+            x[env, rd, slot] = xv[take, 0]
+            v[env, rd, slot] = xv[take, 1]
+            if w is not None:
+                tk = np.zeros(n, np.float32) if spawn is None else np.asarray(spawn, np.float32).reshape(-1)[take]
+                if het:
+                    w[env, rd, slot] = ((tk.astype(np.int64) + shift) & 0xFFFFFF).astype(np.float32)
+                else:
+                    w[env, rd, slot] = tk if shift == 0 else tk + np.float32(shift)
+            if arch is not None:
+                arch[env, rd, slot] = 0 if row is None else np.asarray(row, np.uint8).reshape(-1)[take] & 63
+            x[env, rd, l] = np.inf if lead_x is None else np.asarray(lead_x, np.float32).reshape(-1)[key]
+            ld[env, rd] = l
+            lc[env, rd] = (l + n - 1) % (C - 1) + 1 if n else l
+    return x, v, w, arch, ld.astype(np.int32), lc.astype(np.int32), lost
+
+
 def car_ages(w, leading, lastcar, C, now, het=False):
     """The definition of tfx_car_ages (include/tfx.h) in NumPy, over the ring plane w float32 [..., R, C] of spawn ticks
     by ring slot (what tfx_export_ring produces; heterogeneous handles: the spawn tick modulo 2^24), leading / lastcar

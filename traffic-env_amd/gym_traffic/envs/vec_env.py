@@ -615,6 +615,45 @@ class TrafficVecEnv(object):
             age = torch.where(valid, age, torch.zeros_like(age))
         return VecCars(*cl, sel, road_id, rank, dist, age, valid)
 
+    def set_cars(self, cars, envs=None, roads=None, leading=None, spawn_shift=0):
+        """Write a car list back: what cars() returned, or an edited copy of it (any object with offsets, xv, row and
+        spawn - a VecCars, a CarList, a namedtuple's _replace(...)), becomes the cars of the chosen envs in one launch
+        with no host synchronisation (TfxEngine.put_cars / tfx_put_cars, include/tfx.h).  Road `road` of env envs[s] (None:
+        env s) then holds entries offsets[s * R + road] .. offsets[s * R + road + 1] of the planes, head first: stall a car
+        by zeroing its v, delete or insert cars by rebuilding offsets and planes in torch.  roads: a uint8 / bool mask [R] -
+        roads outside it keep their cars (pass the mask cars() was given); leading int32 [n_sel, R]: the roads' new ring
+        position (None: each road keeps its own, the head car takes the slot behind it); spawn_shift: added to every
+        spawn tick (a list taken at another clock).  envs must be distinct: a host-side list with repeats raises.  A road
+        holds at most capacity - 2 cars: the excess is dropped and counted in engine.put_lost().  Counters, lights,
+        rewards and the trip log are not touched - see pack_envs / unpack_envs for whole envs."""
+        self.engine.put_cars(cars.offsets, cars.xv, row=cars.row, spawn=cars.spawn, env_ids=envs, roads=roads,
+                             leading=leading, spawn_shift=spawn_shift, count_lost=True)
+
+    def pack_envs(self, envs):
+        """Everything a caller can see of the chosen envs as a plain dict of device tensors - for a scenario library, for
+        torch.save, for a send to another rank (TfxEngine.pack_envs): the car list (offsets, xv, row, spawn) with the
+        roads' `leading`, the bound per-env rows gathered by index in torch (obs, rewards, waiting, passed_dst, done_tick,
+        done), on validate envs the trip-log rows and n_trips, and the clock (`tick`), grid and capacity it was taken at.
+        One read-only launch plus torch indexing; the total number of cars is read back once.  envs: a list, an array or a
+        device tensor of env numbers.  What the handle alone owns - the position of an arrival stream, the greedy
+        controller's held action, the episode accounting - is NOT in the dict: tfx.h lets those travel through clone_envs
+        only."""
+        return self.engine.pack_envs(envs)
+
+    def unpack_envs(self, envs, packed):
+        """Write what pack_envs returned into envs of this batch or of another one on the same grid - E and capacity may
+        differ: envs[s] receives selection s of the dict (TfxEngine.unpack_envs).  One launch for the cars plus torch index
+        writes for the per-env rows; no host synchronisation.  A road whose cars do not fit this batch's capacity keeps the
+        first capacity - 2 and the excess shows in engine.put_lost(); `leading` is kept where it is a ring index here.
+        Spawn ticks and the done_tick stamp are rebased by the difference of the two clocks, as clone_envs does across
+        handles, so ages and trip times go on correctly; travel_times() goes on from the end of the log an env received.
+        envs must be distinct.  The arrival stream's position, the greedy controller's held action and the episode
+        accounting do NOT travel this way (tfx.h: clone_envs alone carries them): a written env goes on with its own."""
+        eng = self.engine
+        idx = eng.unpack_envs(envs, packed)
+        if self._travel is not None and eng.n_trips is not None:
+            self._travel["cursor"][idx] = eng.n_trips[idx]
+
     def arterial(self, row_or_col, direction):
         """uint8 [R] road mask of one arterial: the chain of roads a car of `direction` (0 eastbound, 1 westbound - along
         row `row_or_col`; 2 towards higher rows, 3 towards lower rows - along column `row_or_col`) drives through, from
