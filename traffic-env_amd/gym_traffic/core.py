@@ -29,26 +29,76 @@ ARCHETYPE = dict(car_v=11.11, car_l=4.0, car_a=3.0, car_delta=4.0, car_v0=13.89,
 CONSTANTS = dict(yellow_ticks=6, thresh=0.2, detect_dist=10.0, overflow_penalty=10.0, eps=1e-8)
 
 
-# what road_measures() returns: four [E, R] device tensors by road id (tfx_road_measures, include/tfx.h)
-RoadMeasures = collections.namedtuple("RoadMeasures", "n_cars n_halted queue speed_sum")
-# what road_cells() returns: two [E, R, B] device tensors by road id and cell (tfx_road_cells, include/tfx.h)
-RoadCells = collections.namedtuple("RoadCells", "n_cars speed_sum")
-# what car_ages() returns: three [E, R] device tensors by road id (tfx_car_ages, include/tfx.h)
-CarAges = collections.namedtuple("CarAges", "n_cars age_sum age_max")
-# what trip_stats() returns: [E] device tensors, hist [E, n_bins] or None (tfx_trip_stats, include/tfx.h)
-TripStats = collections.namedtuple("TripStats", "count tick_sum tick_max lost hist")
-# what road_following() returns: eleven [E, R] device tensors by road id (tfx_road_following, include/tfx.h)
-RoadFollowing = collections.namedtuple("RoadFollowing", "n_cars n_pairs n_joined n_overlap gap_sum gap_min n_hw hw_sum "
-                                                        "n_conflict ttc_min drac_max")
-_FOLLOW_FLOATS = ("gap_sum", "gap_min", "hw_sum", "ttc_min", "drac_max")
-# what road_ends() returns: n_cars, n_heads int32 [E, R]; heads float32 [E, R, k, 2]; head_rows uint8 [E, R, k]; tail
-# float32 [E, R, 2]; tail_row uint8 [E, R] - device tensors by road id (tfx_road_ends, include/tfx.h)
-RoadEnds = collections.namedtuple("RoadEnds", "n_cars n_heads heads head_rows tail tail_row")
+# One row per device query that writes into a struct of output planes (include/tfx.h).  `tuple` is what the query returns
+# and takes as out=; its fields are those of the ctypes struct `struct`.  `planes` holds per field (torch dtype: the element
+# type of the C member, shape, fill of a fresh tensor); a shape is a function of the engine and the query's key - what the
+# shapes depend on beyond the engine: road_ends' k, the number of bins or cells, car_list's length - and gives None where
+# the engine or the call has no such plane.
+Query = collections.namedtuple("Query", "name tuple struct planes")
+
+
+def _query(name, tuple_name, struct, **planes):
+    fields = [f for f, _ in struct._fields_]
+    if set(fields) != set(planes):
+        raise TypeError("%s: the planes %s are not the fields of %s" % (name, sorted(planes), struct.__name__))
+    return Query(name, collections.namedtuple(tuple_name, fields), struct, tuple(planes[f] for f in fields))
+
+
+def _e(eng, key):
+    return (eng.E,)
+
+
+def _er(eng, key):
+    return (eng.E, eng.R)
+
+
+def _erk(eng, key):
+    return (eng.E, eng.R, key)
+
+
+def _cap(eng, key):
+    return (key,)
+
+
+_I32, _I64, _F32, _U8, _INF = torch.int32, torch.int64, torch.float32, torch.uint8, float("inf")
+QUERIES = {q.name: q for q in (
+    _query("road_measures", "RoadMeasures", nat.TfxMeasureBuffers,
+           n_cars=(_I32, _er, 0), n_halted=(_I32, _er, 0), queue=(_I32, _er, 0), speed_sum=(_F32, _er, 0)),
+    _query("road_following", "RoadFollowing", nat.TfxFollowBuffers,
+           n_cars=(_I32, _er, 0), n_pairs=(_I32, _er, 0), n_joined=(_I32, _er, 0), n_overlap=(_I32, _er, 0),
+           gap_sum=(_F32, _er, 0), gap_min=(_F32, _er, _INF), n_hw=(_I32, _er, 0), hw_sum=(_F32, _er, 0),
+           n_conflict=(_I32, _er, 0), ttc_min=(_F32, _er, _INF), drac_max=(_F32, _er, 0)),
+    _query("road_ends", "RoadEnds", nat.TfxEndsBuffers,
+           n_cars=(_I32, _er, 0), n_heads=(_I32, _er, 0), heads=(_F32, lambda eng, k: (eng.E, eng.R, k, 2), 0),
+           head_rows=(_U8, _erk, 0), tail=(_F32, lambda eng, k: (eng.E, eng.R, 2), 0), tail_row=(_U8, _er, 0)),
+    _query("car_ages", "CarAges", nat.TfxAgeBuffers, n_cars=(_I32, _er, 0), age_sum=(_I64, _er, 0), age_max=(_I32, _er, 0)),
+    _query("trip_stats", "TripStats", nat.TfxTripStatBuffers,
+           count=(_I32, _e, 0), tick_sum=(_I64, _e, 0), tick_max=(_I32, _e, 0), lost=(_I32, _e, 0),
+           hist=(_I32, lambda eng, B: (eng.E, B) if B else None, 0)),
+    _query("road_cells", "RoadCells", nat.TfxCellBuffers, n_cars=(_I32, _erk, 0), speed_sum=(_F32, _erk, 0)),
+    # (never cached: car_list makes fresh planes of the call's length; CarList puts n and offsets in front of them)
+    _query("car_list", "CarPlanes", nat.TfxCarListBuffers,
+           xv=(_F32, lambda eng, cap: (cap, 2), 0), road=(_I32, _cap, 0), row=(_U8, _cap, 0),
+           spawn=(_F32, lambda eng, cap: (cap,) if eng.P == 3 else None, 0)),
+)}
+# road_measures(), road_following(), car_ages(): [E, R] device tensors by road id; road_ends(): heads [E, R, k, 2], head_rows
+# [E, R, k], tail [E, R, 2]; trip_stats(): [E], hist [E, n_bins] or None; road_cells(): [E, R, B] by road id and cell
+RoadMeasures, RoadFollowing, RoadEnds, CarAges, TripStats, RoadCells = [
+    QUERIES[q].tuple for q in ("road_measures", "road_following", "road_ends", "car_ages", "trip_stats", "road_cells")]
 # what car_list() returns: n int32 scalar (the total N) and offsets int32 [n_sel * R + 1], then the planes of max_cars (or N)
-# entries: xv float32 [.., 2], road int32, row uint8, spawn float32 (None on engines without a spawn plane) - device tensors
-# (tfx_car_list, include/tfx.h)
-CarList = collections.namedtuple("CarList", "n offsets xv road row spawn")
-_CAR_PLANES = (("xv", torch.float32, (2,)), ("road", torch.int32, ()), ("row", torch.uint8, ()), ("spawn", torch.float32, ()))
+# entries: xv [.., 2], road, row, spawn (None on engines without a spawn plane) - device tensors
+CarList = collections.namedtuple("CarList", ("n", "offsets") + QUERIES["car_list"].tuple._fields)
+
+
+def _is_plane(t, dtype, shape):
+    """t is a contiguous device tensor of this dtype and shape"""
+    return isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() \
+        and t.is_cuda
+
+
+def _buffers(q, out):
+    """the ctypes struct of query `q` that points at the tensors of `out` (a member None: a null pointer)"""
+    return q.struct(*[_ptr(t) for t in out])
 
 
 def _ptr(t):
@@ -218,13 +268,9 @@ class TfxEngine(object):
         self.passed_dst = torch.zeros((E, I), dtype=torch.uint8, device=dev)
         self.trip_times = torch.zeros((E, self.trip_cap), dtype=torch.float32, device=dev) if validate else None
         self._cars = torch.zeros((E, R), dtype=torch.int32, device=dev)
-        self._measures = None       # road_measures(): made on first use
-        self._ages = None           # car_ages(): made on first use
-        self._following = None      # road_following(): made on first use
-        self._trips = {}            # trip_stats(): made on first use, per number of bins
-        self._cells = {}            # road_cells(): made on first use, per number of cells
-        self._ends = {}             # road_ends(): made on first use, per k
-        self._frames = {}           # frames(): made on first use, per (frames, px); holds the background after that
+        # the queries' default tensors, made on first use: (query, key) -> its tuple of QUERIES; ("frames", (frames, px)) ->
+        # the picture, which holds the background after that
+        self._planes = {}
         b = nat.TfxBuffers()
         b.xv = _ptr(self._t if self._t is not None else self._ring)
         b.w = _ptr(self._tw if self._tw is not None else self._ringw)
@@ -432,6 +478,66 @@ class TfxEngine(object):
             nat.check(self.lib.tfx_clone_skipped(self.h, C.byref(n), self._stream()))
         return int(n.value)
 
+    # ---- what the device queries share (one row of QUERIES each) ----------------------------------------------------
+    def _tensors(self, q, key, out):
+        """The tensors one call of query `q` writes, as q.tuple.  out None: those the engine allocates on first use of
+        (q, key) - filled as the row says - and reuses; otherwise the caller's, every member that is not None checked
+        against the row: a contiguous device tensor of the plane's dtype and shape."""
+        if out is None:
+            out = self._planes.get((q.name, key))
+            if out is None:
+                out = self._planes[(q.name, key)] = self._fresh(q, key)
+            return out
+        out = q.tuple(*out)
+        for name, (dtype, shape, _), t in zip(q.tuple._fields, q.planes, out):
+            if t is not None:
+                shape = shape(self, key)
+                if shape is None:
+                    raise ValueError("%s(out=): %s is a plane this engine or call does not have" % (q.name, name))
+                if not _is_plane(t, dtype, shape):
+                    raise ValueError("%s(out=): %s must be a contiguous %s %s device tensor" % (q.name, name, dtype, list(shape)))
+        return out
+
+    def _fresh(self, q, key):
+        """new tensors for every plane of query `q` that this engine has at `key`, filled as the row says"""
+        planes = []
+        for dtype, shape, fill in q.planes:
+            shape = shape(self, key)
+            if shape is None:
+                planes.append(None)
+            elif fill == 0:
+                planes.append(torch.zeros(shape, dtype=dtype, device=self.device))
+            else:
+                planes.append(torch.full(shape, fill, dtype=dtype, device=self.device))
+        return q.tuple(*planes)
+
+    def _launch_report(self, fn, *ints):
+        """(workgroups, wavefronts) as one of the library's tfx_*_launch calls reports them for this engine"""
+        g, w = C.c_int32(), C.c_int32()
+        nat.check(fn(self.h, *ints, C.byref(g), C.byref(w)))
+        return int(g.value), int(w.value)
+
+    def _env_ids(self, env_ids):
+        """a caller's env numbers - a list, an array or a device tensor; None: every env in order - as (int32 device
+        tensor or None, number of selections)"""
+        if env_ids is None:
+            return None, self.E
+        if not torch.is_tensor(env_ids):
+            env_ids = torch.as_tensor(np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1)))
+        ids = env_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        return ids, int(ids.shape[0])
+
+    def _road_mask(self, roads, who):
+        """a caller's uint8 / bool mask [R] by road id (None: every road) as a uint8 device tensor or None"""
+        if roads is None:
+            return None
+        if not torch.is_tensor(roads):
+            roads = torch.as_tensor(np.ascontiguousarray(np.asarray(roads).reshape(-1) != 0))
+        mask = (roads.to(device=self.device).reshape(-1) != 0).to(torch.uint8).contiguous()
+        if int(mask.shape[0]) != self.R:
+            raise ValueError("%s: roads must have %d entries, one per road id" % (who, self.R))
+        return mask
+
     def road_measures(self, halt_speed=0.1, x_from=None, accumulate=False, out=None):
         """The standard traffic measures per road, from one read-only launch over the live cars (tfx_road_measures,
         include/tfx.h; gym_traffic.devrng.road_measures states the definition in NumPy): -> RoadMeasures(n_cars,
@@ -441,21 +547,9 @@ class TfxEngine(object):
         the tensors instead of overwriting them (integrate over decisions by measuring between calls).  out: the
         caller's RoadMeasures (any member None: not computed); default: tensors the engine allocates once, zeroed,
         and reuses.  No host synchronisation; nothing of the env state is written."""
-        if out is None:
-            if self._measures is None:
-                i32 = [torch.zeros((self.E, self.R), dtype=torch.int32, device=self.device) for _ in range(3)]
-                self._measures = RoadMeasures(*i32, torch.zeros((self.E, self.R), dtype=torch.float32, device=self.device))
-            out = self._measures
-        else:
-            out = RoadMeasures(*out)
-            for name, t in zip(RoadMeasures._fields, out):
-                want = torch.float32 if name == "speed_sum" else torch.int32
-                if t is not None and (t.dtype != want or tuple(t.shape) != (self.E, self.R) or not t.is_contiguous()
-                                      or not t.is_cuda):
-                    raise ValueError("road_measures(out=): %s must be a contiguous %s [%d, %d] device tensor"
-                                     % (name, want, self.E, self.R))
-        b = nat.TfxMeasureBuffers()
-        b.n_cars, b.n_halted, b.queue, b.speed_sum = [_ptr(t) for t in out]
+        q = QUERIES["road_measures"]
+        out = self._tensors(q, None, out)
+        b = _buffers(q, out)
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_road_measures(self.h, float(halt_speed), float("-inf") if x_from is None else float(x_from),
                                                  C.byref(b), nat.MEASURE_ACCUMULATE if accumulate else 0, self._stream()))
@@ -463,9 +557,7 @@ class TfxEngine(object):
 
     def measure_launch(self):
         """(workgroups, wavefronts) of the road_measures launch of this engine (tfx_measure_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_measure_launch(self.h, C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_measure_launch)
 
     def road_following(self, platoon_gap, v_min, ttc_crit, x_from=None, out=None, accumulate=False):
         """The car-following measures per road, from one read-only launch over the live cars (tfx_road_following,
@@ -479,23 +571,11 @@ class TfxEngine(object):
         overwritten.  out: the caller's RoadFollowing (any member None: not computed; for accumulate the caller starts
         gap_min / ttc_min at +inf and the rest at 0); default: tensors the engine allocates once - zeros, gap_min and
         ttc_min +inf - and reuses.  No host synchronisation; nothing of the env state is written."""
-        want = {f: torch.float32 if f in _FOLLOW_FLOATS else torch.int32 for f in RoadFollowing._fields}
-        if out is None:
-            if self._following is None:
-                self._following = RoadFollowing(*[
-                    torch.full((self.E, self.R), float("inf") if f in ("gap_min", "ttc_min") else 0, dtype=want[f],
-                               device=self.device) for f in RoadFollowing._fields])
-            out = self._following
-        else:
-            out = RoadFollowing(*out)
-            for name, t in zip(RoadFollowing._fields, out):
-                if t is not None and (t.dtype != want[name] or tuple(t.shape) != (self.E, self.R) or not t.is_contiguous()
-                                      or not t.is_cuda):
-                    raise ValueError("road_following(out=): %s must be a contiguous %s [%d, %d] device tensor"
-                                     % (name, want[name], self.E, self.R))
+        q = QUERIES["road_following"]
+        out = self._tensors(q, None, out)
         p = nat.TfxFollowParams(float("-inf") if x_from is None else float(x_from), float(platoon_gap), float(v_min),
                                 float(ttc_crit))
-        b = nat.TfxFollowBuffers(*[_ptr(t) for t in out])
+        b = _buffers(q, out)
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_road_following(self.h, C.byref(p), C.byref(b),
                                                   nat.FOLLOW_ACCUMULATE if accumulate else 0, self._stream()))
@@ -503,9 +583,7 @@ class TfxEngine(object):
 
     def follow_launch(self):
         """(workgroups, wavefronts) of the road_following launch of this engine (tfx_follow_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_follow_launch(self.h, C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_follow_launch)
 
     def road_ends(self, k=4, pad_dist=float("inf"), pad_v=0.0, pad_tail_x=float("inf"), out=None):
         """The two ends of every road, from one read-only launch (tfx_road_ends, include/tfx.h; gym_traffic.devrng.road_ends
@@ -519,31 +597,17 @@ class TfxEngine(object):
         k = int(k)
         if not 1 <= k <= nat.MAX_HEADS:
             raise ValueError("road_ends: k %d is outside 1..%d" % (k, nat.MAX_HEADS))
-        E, R = self.E, self.R
-        want = dict(n_cars=(torch.int32, (E, R)), n_heads=(torch.int32, (E, R)), heads=(torch.float32, (E, R, k, 2)),
-                    head_rows=(torch.uint8, (E, R, k)), tail=(torch.float32, (E, R, 2)), tail_row=(torch.uint8, (E, R)))
-        if out is None:
-            if k not in self._ends:
-                self._ends[k] = RoadEnds(*[torch.zeros(want[f][1], dtype=want[f][0], device=self.device)
-                                           for f in RoadEnds._fields])
-            out = self._ends[k]
-        else:
-            out = RoadEnds(*out)
-            for name, t in zip(RoadEnds._fields, out):
-                dtype, shape = want[name]
-                if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
-                    raise ValueError("road_ends(out=): %s must be a contiguous %s %s device tensor" % (name, dtype, list(shape)))
+        q = QUERIES["road_ends"]
+        out = self._tensors(q, k, out)
         p = nat.TfxEndsParams(k, float(pad_dist), float(pad_v), float(pad_tail_x))
-        b = nat.TfxEndsBuffers(*[_ptr(t) for t in out])
+        b = _buffers(q, out)
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_road_ends(self.h, C.byref(p), C.byref(b), 0, self._stream()))
         return out
 
     def ends_launch(self, k):
         """(workgroups, wavefronts) of the road_ends launch of this engine for k cars a road (tfx_ends_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_ends_launch(self.h, int(k), C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_ends_launch, int(k))
 
     def car_list(self, env_ids=None, roads=None, max_cars=None, out=None):
         """Every live car of chosen envs as one flat run, from one read-only launch (tfx_car_list, include/tfx.h;
@@ -559,27 +623,17 @@ class TfxEngine(object):
         on are not written (fresh tensors are zeroed).  max_cars = None: n is read back once - ONE host synchronisation -
         and the planes are sized exactly.  out: the caller's (xv, road, row, spawn) of one length, any member None: not
         computed; then max_cars is that length.  Nothing of the env state is written."""
-        E, R, dev = self.E, self.R, self.device
+        q, E, R, dev = QUERIES["car_list"], self.E, self.R, self.device
         ld, lc = self.leading, self.lastcar
         count = (lc - ld + (ld > lc).to(torch.int32) * (self.C - 1)).clamp_(0, self.C - 1)
-        if env_ids is None:
-            ids, n_sel = None, E
-        else:
-            if not torch.is_tensor(env_ids):
-                env_ids = torch.as_tensor(np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1)))
-            ids = env_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-            n_sel = int(ids.shape[0])
-            if n_sel < 1:
-                raise ValueError("car_list: no env chosen")
+        ids, n_sel = self._env_ids(env_ids)
+        if n_sel < 1:
+            raise ValueError("car_list: no env chosen")
+        if ids is not None:
             shown = (ids >= 0) & (ids < E)
             count = count.index_select(0, torch.where(shown, ids, torch.zeros_like(ids)).long()) * shown[:, None]
-        mask = None
-        if roads is not None:
-            if not torch.is_tensor(roads):
-                roads = torch.as_tensor(np.ascontiguousarray(np.asarray(roads).reshape(-1) != 0))
-            mask = (roads.to(device=dev).reshape(-1) != 0).to(torch.uint8).contiguous()
-            if int(mask.shape[0]) != R:
-                raise ValueError("car_list: roads must have %d entries, one per road id" % R)
+        mask = self._road_mask(roads, "car_list")
+        if mask is not None:
             count = count * mask[None, :]
         if n_sel * R + 1 > 2 ** 31 - 1:
             raise ValueError("car_list: %d selections of %d roads do not fit int32 offsets" % (n_sel, R))
@@ -591,25 +645,17 @@ class TfxEngine(object):
             sizes = {int(t.shape[0]) for t in planes if t is not None}
             if len(planes) != 4 or len(sizes) != 1:
                 raise ValueError("car_list(out=): (xv, road, row, spawn) of one length are needed, any of them None")
-            cap = sizes.pop()
-            if max_cars is not None and int(max_cars) != cap:
-                raise ValueError("car_list(out=): max_cars %d is not the tensors' length %d" % (int(max_cars), cap))
-            for (name, dtype, tail), t in zip(_CAR_PLANES, planes):
-                if t is not None and (t.dtype != dtype or tuple(t.shape) != (cap,) + tail or not t.is_contiguous()
-                                      or not t.is_cuda):
-                    raise ValueError("car_list(out=): %s must be a contiguous %s %s device tensor"
-                                     % (name, dtype, [cap] + list(tail)))
-            if planes[3] is not None and self.P != 3:
-                raise ValueError("car_list(out=): the engine keeps no spawn ticks (planes == 2)")
+            cap = sizes.pop() if max_cars is None else int(max_cars)
+            # (refused: a length that is not max_cars; spawn on an engine that keeps no spawn ticks, planes == 2)
+            planes = self._tensors(q, cap, planes)
         else:
             cap = int(n) if max_cars is None else int(max_cars)      # int(n): the one host synchronisation
             if cap < 0:
                 raise ValueError("car_list: max_cars %d is negative" % cap)
-            planes = [torch.zeros((cap,) + tail, dtype=dtype, device=dev) if (name != "spawn" or self.P == 3) else None
-                      for name, dtype, tail in _CAR_PLANES]
+            planes = self._fresh(q, cap)
         if cap > 2 ** 31 - 1:
             raise ValueError("car_list: %d entries do not fit int32 offsets" % cap)
-        b = nat.TfxCarListBuffers(*[_ptr(t) for t in planes])
+        b = _buffers(q, planes)
         with torch.cuda.device(dev):
             nat.check(self.lib.tfx_car_list(self.h, _ptr(ids), n_sel, _ptr(mask), _ptr(offsets), cap, C.byref(b), 0,
                                             self._stream()))
@@ -618,19 +664,18 @@ class TfxEngine(object):
     def car_list_launch(self, n_sel):
         """(workgroups, wavefronts) of the car_list launch of this engine for n_sel chosen envs (tfx_car_list_launch;
         tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_car_list_launch(self.h, int(n_sel), C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_car_list_launch, int(n_sel))
 
-    def _dev(self, a, dtype, np_dtype, shape, what):
-        """a caller's tensor or array-like as a contiguous device tensor of this dtype and shape (None stays None)"""
+    def _dev(self, who, a, dtype, np_dtype, shape, what):
+        """argument `what` of method `who` - a caller's tensor or array-like - as a contiguous device tensor of this dtype
+        and shape (None stays None)"""
         if a is None:
             return None
         if not torch.is_tensor(a):
             a = torch.as_tensor(np.ascontiguousarray(np.asarray(a, np_dtype)))
         a = a.to(device=self.device, dtype=dtype).contiguous()
         if tuple(a.shape) != tuple(shape):
-            raise ValueError("put_cars: %s must have shape %s, not %s" % (what, list(shape), list(a.shape)))
+            raise ValueError("%s: %s must have shape %s, not %s" % (who, what, list(shape), list(a.shape)))
         return a
 
     def put_cars(self, offsets, xv=None, row=None, spawn=None, env_ids=None, roads=None, leading=None, lead_x=None,
@@ -661,37 +706,28 @@ class TfxEngine(object):
         if n_keys < R or n_keys % R:
             raise ValueError("put_cars: offsets must hold n_sel * %d + 1 entries, not %d" % (R, n_keys + 1))
         n_sel = n_keys // R
-        ids = None
-        if env_ids is not None:
-            if not torch.is_tensor(env_ids):
-                host_ids = np.asarray(env_ids, np.int64).reshape(-1)
-                shown = host_ids[(host_ids >= 0) & (host_ids < self.E)]
-                if len(np.unique(shown)) != len(shown):
-                    raise ValueError("put_cars: env_ids must be distinct")
-                env_ids = torch.as_tensor(np.ascontiguousarray(host_ids.astype(np.int32)))
-            ids = env_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-            if int(ids.shape[0]) != n_sel:
-                raise ValueError("put_cars: %d env ids for offsets of %d selections" % (int(ids.shape[0]), n_sel))
-        elif n_sel > self.E:
+        if env_ids is not None and not torch.is_tensor(env_ids):
+            env_ids = np.asarray(env_ids, np.int64).reshape(-1)
+            shown = env_ids[(env_ids >= 0) & (env_ids < self.E)]
+            if len(np.unique(shown)) != len(shown):
+                raise ValueError("put_cars: env_ids must be distinct")
+        ids, n_ids = self._env_ids(env_ids)
+        if ids is not None and n_ids != n_sel:
+            raise ValueError("put_cars: %d env ids for offsets of %d selections" % (n_ids, n_sel))
+        if ids is None and n_sel > self.E:
             raise ValueError("put_cars: offsets of %d selections for %d envs" % (n_sel, self.E))
-        mask = None
-        if roads is not None:
-            if not torch.is_tensor(roads):
-                roads = torch.as_tensor(np.ascontiguousarray(np.asarray(roads).reshape(-1) != 0))
-            mask = (roads.to(device=dev).reshape(-1) != 0).to(torch.uint8).contiguous()
-            if int(mask.shape[0]) != R:
-                raise ValueError("put_cars: roads must have %d entries, one per road id" % R)
+        mask = self._road_mask(roads, "put_cars")
         if not torch.is_tensor(xv):
             xv = torch.as_tensor(np.ascontiguousarray(np.asarray(xv, np.float32).reshape(-1, 2)))
         xv = xv.to(device=dev, dtype=torch.float32).contiguous()
         cap = int(xv.shape[0])
         if xv.dim() != 2 or xv.shape[1] != 2 or cap > 2 ** 31 - 1:
             raise ValueError("put_cars: xv must be [cap, 2] with cap below 2^31")
-        row = self._dev(row, torch.uint8, np.uint8, (cap,), "row")
-        spawn = self._dev(spawn, torch.float32, np.float32, (cap,), "spawn") if self.P == 3 else None
-        leading = self._dev(None if leading is None else leading.reshape(-1) if torch.is_tensor(leading)
+        row = self._dev("put_cars", row, torch.uint8, np.uint8, (cap,), "row")
+        spawn = self._dev("put_cars", spawn, torch.float32, np.float32, (cap,), "spawn") if self.P == 3 else None
+        leading = self._dev("put_cars", None if leading is None else leading.reshape(-1) if torch.is_tensor(leading)
                             else np.asarray(leading).reshape(-1), torch.int32, np.int32, (n_keys,), "leading")
-        lead_x = self._dev(None if lead_x is None else lead_x.reshape(-1) if torch.is_tensor(lead_x)
+        lead_x = self._dev("put_cars", None if lead_x is None else lead_x.reshape(-1) if torch.is_tensor(lead_x)
                            else np.asarray(lead_x).reshape(-1), torch.float32, np.float32, (n_keys,), "lead_x")
         if count_lost and getattr(self, "_put_lost", None) is None:
             self._put_lost = torch.zeros((1,), dtype=torch.int64, device=dev)
@@ -770,9 +806,7 @@ class TfxEngine(object):
 
     def put_launch(self, n_sel):
         """(workgroups, wavefronts) of the put_cars launch of this engine for n_sel chosen envs (tfx_put_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_put_launch(self.h, int(n_sel), C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_put_launch, int(n_sel))
 
     def car_ages(self, accumulate=False, out=None):
         """How long every live car has been on the map, per road, from one read-only launch over the side plane
@@ -782,30 +816,16 @@ class TfxEngine(object):
         are added to and age_max is maxed instead of overwritten.  out: the caller's CarAges (any member None: not
         computed); default: tensors the engine allocates once, zeroed, and reuses.  Needs the side plane (planes == 3:
         validate mode or heterogeneous cars).  No host synchronisation; nothing of the env state is written."""
-        want = dict(n_cars=torch.int32, age_sum=torch.int64, age_max=torch.int32)
-        if out is None:
-            if self._ages is None:
-                self._ages = CarAges(*[torch.zeros((self.E, self.R), dtype=want[f], device=self.device)
-                                       for f in CarAges._fields])
-            out = self._ages
-        else:
-            out = CarAges(*out)
-            for name, t in zip(CarAges._fields, out):
-                if t is not None and (t.dtype != want[name] or tuple(t.shape) != (self.E, self.R) or not t.is_contiguous()
-                                      or not t.is_cuda):
-                    raise ValueError("car_ages(out=): %s must be a contiguous %s [%d, %d] device tensor"
-                                     % (name, want[name], self.E, self.R))
-        b = nat.TfxAgeBuffers()
-        b.n_cars, b.age_sum, b.age_max = [_ptr(t) for t in out]
+        q = QUERIES["car_ages"]
+        out = self._tensors(q, None, out)
+        b = _buffers(q, out)
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_car_ages(self.h, C.byref(b), nat.TRAVEL_ACCUMULATE if accumulate else 0, self._stream()))
         return out
 
     def ages_launch(self):
         """(workgroups, wavefronts) of the car_ages launch of this engine (tfx_ages_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_ages_launch(self.h, C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_ages_launch)
 
     def trip_stats(self, edges=None, cursor=None, accumulate=False, out=None):
         """The finished trips of every env, reduced on the device where they are logged (tfx_trip_stats, include/tfx.h;
@@ -822,26 +842,11 @@ class TfxEngine(object):
         if e is not None and not 1 <= B <= nat.MAX_TRIP_BINS:
             raise ValueError("trip_stats: %d edges - 2 .. %d make 1 .. %d bins" % (len(e), nat.MAX_TRIP_BINS + 1,
                                                                                   nat.MAX_TRIP_BINS))
-        want = dict(count=torch.int32, tick_sum=torch.int64, tick_max=torch.int32, lost=torch.int32, hist=torch.int32)
-        shape = lambda f: (self.E, B) if f == "hist" else (self.E,)   # noqa: E731
-        if out is None:
-            if B not in self._trips:
-                self._trips[B] = TripStats(*[None if (f == "hist" and B == 0) else
-                                             torch.zeros(shape(f), dtype=want[f], device=self.device)
-                                             for f in TripStats._fields])
-            out = self._trips[B]
-        else:
-            out = TripStats(*out)
-            for name, t in zip(TripStats._fields, out):
-                if t is not None and (t.dtype != want[name] or tuple(t.shape) != shape(name) or not t.is_contiguous()
-                                      or not t.is_cuda):
-                    raise ValueError("trip_stats(out=): %s must be a contiguous %s %s device tensor"
-                                     % (name, want[name], list(shape(name))))
-        if cursor is not None and (not isinstance(cursor, torch.Tensor) or cursor.dtype != torch.int32
-                                   or tuple(cursor.shape) != (self.E,) or not cursor.is_contiguous() or not cursor.is_cuda):
+        q = QUERIES["trip_stats"]
+        out = self._tensors(q, B, out)
+        if cursor is not None and not _is_plane(cursor, torch.int32, (self.E,)):
             raise ValueError("trip_stats(cursor=): a contiguous int32 [%d] device tensor is needed" % self.E)
-        b = nat.TfxTripStatBuffers()
-        b.count, b.tick_sum, b.tick_max, b.lost, b.hist = [_ptr(t) for t in out]
+        b = _buffers(q, out)
         ep = None if e is None else e.ctypes.data_as(C.POINTER(C.c_int32))
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_trip_stats(self.h, ep, B, _ptr(cursor), C.byref(b),
@@ -858,23 +863,11 @@ class TfxEngine(object):
         allocates once per B, zeroed, and reuses.  No host synchronisation; nothing of the env state is written."""
         e = np.ascontiguousarray(np.asarray(edges, np.float32).reshape(-1))
         B = len(e) - 1
-        shape = (self.E, self.R, B)
         if not 1 <= B <= nat.MAX_CELLS:
             raise ValueError("road_cells: %d edges - 2 .. %d make 1 .. %d cells" % (len(e), nat.MAX_CELLS + 1, nat.MAX_CELLS))
-        if out is None:
-            if B not in self._cells:
-                self._cells[B] = RoadCells(torch.zeros(shape, dtype=torch.int32, device=self.device),
-                                           torch.zeros(shape, dtype=torch.float32, device=self.device))
-            out = self._cells[B]
-        else:
-            out = RoadCells(*out)
-            for name, t in zip(RoadCells._fields, out):
-                want = torch.float32 if name == "speed_sum" else torch.int32
-                if t is not None and (t.dtype != want or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
-                    raise ValueError("road_cells(out=): %s must be a contiguous %s [%d, %d, %d] device tensor"
-                                     % ((name, want) + shape))
-        b = nat.TfxCellBuffers()
-        b.n_cars, b.speed_sum = [_ptr(t) for t in out]
+        q = QUERIES["road_cells"]
+        out = self._tensors(q, B, out)
+        b = _buffers(q, out)
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_road_cells(self.h, e.ctypes.data_as(C.POINTER(C.c_float)), B, C.byref(b),
                                               nat.CELLS_ACCUMULATE if accumulate else 0, self._stream()))
@@ -882,9 +875,7 @@ class TfxEngine(object):
 
     def cells_launch(self, n_cells):
         """(workgroups, wavefronts) of the road_cells launch of this engine for n_cells cells (tfx_cells_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_cells_launch(self.h, int(n_cells), C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_cells_launch, int(n_cells))
 
     def frame_size(self, px=32):
         """(H, W) of a frame at px pixels per road length (tfx_frame_size): ((m + 1) * px + 1, (n + 1) * px + 1)."""
@@ -901,13 +892,7 @@ class TfxEngine(object):
         `out` already holds the background of an earlier call with the same px, write the road pixels only.  Default:
         a tensor the engine keeps per (n, px) and reuses - from its second use on only the road pixels are written.
         No host synchronisation when env_ids is None or a device tensor; nothing of the env state is written."""
-        if env_ids is None:
-            ids, n = None, self.E
-        else:
-            if not torch.is_tensor(env_ids):
-                env_ids = torch.as_tensor(np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1)))
-            ids = env_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-            n = int(ids.shape[0])
+        ids, n = self._env_ids(env_ids)
         px = int(px)
         if not nat.FRAME_PX_MIN <= px <= nat.FRAME_PX_MAX:
             raise ValueError("frames: px must be in %d .. %d" % (nat.FRAME_PX_MIN, nat.FRAME_PX_MAX))
@@ -915,11 +900,11 @@ class TfxEngine(object):
             raise ValueError("frames: no env to draw")
         shape = (n,) + self.frame_size(px) + (4,)
         if out is None:
-            roads_only = (n, px) in self._frames
+            roads_only = ("frames", (n, px)) in self._planes
             if not roads_only:
-                self._frames[(n, px)] = torch.empty(shape, dtype=torch.uint8, device=self.device)
-            out = self._frames[(n, px)]
-        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+                self._planes[("frames", (n, px))] = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            out = self._planes[("frames", (n, px))]
+        elif not _is_plane(out, torch.uint8, shape):
             raise ValueError("frames(out=): a contiguous uint8 [%d, %d, %d, 4] device tensor is needed" % shape[:3])
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_frames(self.h, _ptr(ids), n, px, _ptr(out), nat.FRAMES_ROADS_ONLY if roads_only else 0,
@@ -928,9 +913,7 @@ class TfxEngine(object):
 
     def frames_launch(self, n_frames, px=32):
         """(workgroups, wavefronts) of the frames launch of this engine for n_frames frames (tfx_frames_launch; tests)."""
-        g, w = C.c_int32(), C.c_int32()
-        nat.check(self.lib.tfx_frames_launch(self.h, int(n_frames), int(px), C.byref(g), C.byref(w)))
-        return int(g.value), int(w.value)
+        return self._launch_report(self.lib.tfx_frames_launch, int(n_frames), int(px))
 
     def head_rows(self):
         """uint8 [E,R] (host): rows at the top of each road's column that hold no car (tfx_debug_head_rows; tests)."""
@@ -1012,8 +995,7 @@ class TfxEngine(object):
         if profile_of_env is None:
             profile_of_env = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
         prof = profile_of_env
-        if not isinstance(prof, torch.Tensor) or prof.dtype != torch.int32 or tuple(prof.shape) != (self.E,) \
-                or not prof.is_cuda or not prof.is_contiguous():
+        if not _is_plane(prof, torch.int32, (self.E,)):
             raise ValueError("profile_of_env must be a contiguous int32 [%d] device tensor" % self.E)
         cc = np.ascontiguousarray(tables.count_cdf, np.uint32)
         rc = np.ascontiguousarray(tables.road_cdf, np.uint32)
@@ -1044,7 +1026,7 @@ class TfxEngine(object):
         shape = (int(n_ticks), self.E, self.n_entry)
         if out is None:
             out = torch.empty(shape, dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous():
+        elif not _is_plane(out, torch.int32, shape):
             raise ValueError("demand_counts(out=): a contiguous int32 [%d, %d, %d] device tensor" % shape)
         if shape[0] == 0:
             return out                  # (an empty tensor has no address to hand over)
@@ -1068,8 +1050,7 @@ class TfxEngine(object):
             rows = torch.zeros(shape, dtype=torch.uint8, device=self.device)
         else:
             counts, rows = out
-            if counts.dtype != torch.int32 or tuple(counts.shape) != shape[:3] or rows.dtype != torch.uint8 or tuple(rows.shape) != shape \
-                    or not (counts.is_cuda and rows.is_cuda and counts.is_contiguous() and rows.is_contiguous()):
+            if not (_is_plane(counts, torch.int32, shape[:3]) and _is_plane(rows, torch.uint8, shape)):
                 raise ValueError("demand_rows(out=): contiguous device tensors int32 [%d, %d, %d] and uint8 [%d, %d, %d, %d]"
                                  % (shape[:3] + shape))
         if rows.numel() == 0:           # (no ticks, or n_cdf = 1: no cars at all - an empty tensor has no address)
