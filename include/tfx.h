@@ -48,6 +48,29 @@ extern "C" {
 #define TFX_ABI_VERSION 13
 #define TFX_KP 2 /* popped cars carried per road per tick on the parallel path; more -> exact serial path */
 #define TFX_MAX_ARCH 64 /* rows of the archetype table (traffic_env.py:35-43 ships one); a power of two */
+/* The clock's domain: 0 <= tick <= TFX_TICK_MAX, for the handle's clock between calls and for every tick a call runs.
+ * tfx_set_tick refuses anything else (TFX_EINVAL); a call that would run a tick past it - tfx_step, tfx_agent_step
+ * with clock + n_ticks > TFX_TICK_MAX, tfx_move_cars and tfx_advance_finished_cars at TFX_TICK_MAX - returns TFX_ESTATE
+ * with a message naming the clock, before anything is enqueued: the handle, its clock and the bound buffers stay as
+ * they are, and tfx_set_tick or tfx_reset make it usable again.  The handle checks a host mirror of the device clock
+ * (csrc/tfx_handle.hpp).  The pure previews tfx_demand_counts / tfx_demand_rows take any int32 tick0.
+ *
+ * Where the bound comes from - every int32 expression in csrc/ that adds to a tick t of the domain:
+ *   t + 1            tick stamps, 0 = never (done_tick, the handle's serial-advance and risk stamps, k_res's overflow and
+ *                    serial stamps), the greedy controller's (t + 1) % spacing, k_tail's second tick
+ *   t + 2, t + u     k_tail (u < 2) and the clock a pair leaves; k_res's tick0 + tt and tick0 + n_ticks: all at most the
+ *                    clock the call ends on, which the check keeps at or below TFX_TICK_MAX; k_tail's risk stamp for the
+ *                    pair that follows in the same call, (t + 2) + 1: at most that clock, too
+ *   t + (env + env_id_offset) % period     TFX_ACTION_CYCLE: at most t + TFX_PERIOD_MAX - 1 (tfx_set_actions refuses a
+ *                    longer cycle), the largest of them all: TFX_TICK_MAX + TFX_PERIOD_MAX - 1 = INT32_MAX - 1
+ *   s + (tick(dst) - tick(src))            tfx_clone_envs rebasing a stamp s <= tick(src) + 1: at most tick(dst) + 1
+ *   spawn tick + (tick(dst) - tick(src))   rebasing a heterogeneous side word (tfx_clone_envs, tfx_put_cars' spawn_shift): a
+ *                    24-bit tick plus up to TFX_TICK_MAX passes INT32_MAX - added as unsigned, kept modulo 2^24
+ *   t + tick_offset, first + row           the demand rule: in 64 bits / unsigned, any int32
+ * t % period (periodic spawns) and (float)t (spawn ticks) add nothing; a negative t would break the first (C's % is
+ * negative then) and the stamps (a stamp of tick -1 is 0, "never"), hence the lower bound. */
+#define TFX_PERIOD_MAX (1 << 20)                  /* the longest TFX_ACTION_CYCLE period */
+#define TFX_TICK_MAX (0x7fffffff - TFX_PERIOD_MAX) /* 2146435071 */
 
 enum {
   TFX_OK = 0,
@@ -161,6 +184,8 @@ int tfx_reset_envs(tfx_handle h, const int32_t *phase_init, const uint8_t *mask,
  * per-road tail cache the light kernel reads. */
 int tfx_refresh(tfx_handle h, void *stream);
 
+/* period: TFX_ACTION_CYCLE's cycle, 1 .. TFX_PERIOD_MAX (the bound TFX_TICK_MAX is derived from: the rule adds up to
+ * period - 1 to the clock), and TFX_ACTION_GREEDY's spacing, >= 1; anything else is TFX_EINVAL. */
 int tfx_set_actions(tfx_handle h, int32_t mode, const int32_t *dev, int32_t period, int32_t per_tick);
 int tfx_set_spawns(tfx_handle h, int32_t mode, const int32_t *dev, int32_t period, int32_t per_tick);
 /* On-device form of the reference's Poisson generator (traffic_env.py:160-164): per env, gaps of
@@ -399,7 +424,8 @@ int tfx_cars_on_roads(tfx_handle h, int32_t *out, void *stream);
 int tfx_done(tfx_handle h, uint8_t *out, int32_t since_tick, void *stream);
 
 int tfx_get_tick(tfx_handle h, int32_t *tick);              /* TrafficEnv.steps */
-int tfx_set_tick(tfx_handle h, int32_t tick);               /* also clears the per-env overflow stamps */
+/* also clears the per-env overflow stamps; TFX_EINVAL (nothing changes) outside 0 .. TFX_TICK_MAX */
+int tfx_set_tick(tfx_handle h, int32_t tick);
 /* live cars advanced by move_cars since the last tfx_reset_counters (synchronises the stream) */
 int tfx_vehicle_updates(tfx_handle h, uint64_t *out, void *stream);
 int tfx_reset_counters(tfx_handle h, void *stream);
@@ -682,6 +708,13 @@ int tfx_frames_launch(tfx_handle h, int32_t n_frames, int32_t px, int32_t *grid,
  * in seconds advance_hack would log if the car left the map in this tick:
  *   single-archetype handles   (int32)((float)now - w)               w: the spawn tick, a float
  *   heterogeneous handles      (now - spawn tick) & 0xFFFFFF          spawn ticks are kept modulo 2^24
+ * Late clocks.  A single-archetype handle stores the spawn tick as a float32: (float)tick at the spawn, one rounding to
+ * nearest even, and a logged trip time is ((float)pop tick - w) / 2 in float32.  While the clock is at most 2^24 both
+ * are exact integers and ages and trip times are exact.  Beyond 2^24 they are the values of these formulas and no more:
+ * between 2^24 and 2^25 ticks are kept to the even ones, up to 2^26 to multiples of 4, ... and of 128 at the top of the
+ * clock's domain; an age or a doubled trip time is then off by up to that step.  Heterogeneous handles keep integers
+ * modulo 2^24 and are exact at any clock of the domain for trips (and ages) shorter than 2^24 ticks.  Rebasing
+ * (tfx_clone_envs, tfx_put_cars' spawn_shift) gives a single-archetype spawn tick (float)(w + dt), rounded once.
  * Per road:
  *   n_cars    the cars on the road, what tfx_cars_on_roads returns
  *   age_sum   the int64 sum of their ages

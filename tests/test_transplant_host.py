@@ -238,7 +238,9 @@ def dropped_tails(leading, lastcar, pick, C):
 # ---- the checker's side ------------------------------------------------------------------------------------------------------
 class OracleSide(object):
     """A batched OracleEnv that executes the ops; `done`: the envs that overflowed in the last call (what the engine's
-    `done` holds), `ever`: in any call so far, `pops`: the most cars one road handed on, per tick run so far."""
+    `done` holds), `ever`: in any call so far, `pops`: the most cars one road handed on, per tick run so far.  on_tick:
+    called behind every tick the oracle runs, with the clock that tick ran at (tests/test_late_clock_host.py dates the
+    trip log with it)."""
 
     def __init__(self, world):
         self.w, self.orc = world, world.oracle()
@@ -247,6 +249,7 @@ class OracleSide(object):
         self.ever = np.zeros(world.E, bool)
         self.pops = []
         self.outs = None
+        self.on_tick = None
 
     def run(self, ops):
         for op in ops:
@@ -276,6 +279,8 @@ class OracleSide(object):
         off, roads = csr(cnt, w.entry)
         done = o.step(act, (off, roads), spawn_arch=rows_of(cnt, rows, off) if w.het else None, archetypes=w.tab10)[2]
         self.pops.append(int(o.passed.max()))
+        if self.on_tick is not None:
+            self.on_tick(self.tick)
         self.tick += 1
         return done.astype(bool)
 
@@ -294,10 +299,16 @@ class OracleSide(object):
 
     def _agent(self, op):
         w = self.w
-        aobs, arew, adone, _ = emulate_decision(self.orc, self.tick, op["act"],
-                                                lambda t, frozen: (op["cnt"][t], op["rows"][t] if w.het else None),
-                                                op["n"], op["remi"], w.tab10)
+
+        def arrivals(t, frozen):                          # (asked for when tick t begins: tick t - 1 is through)
+            if t > 0 and self.on_tick is not None:
+                self.on_tick(self.tick + t - 1)
+            return op["cnt"][t], op["rows"][t] if w.het else None
+
+        aobs, arew, adone, _ = emulate_decision(self.orc, self.tick, op["act"], arrivals, op["n"], op["remi"], w.tab10)
         self.tick += op["n"]
+        if self.on_tick is not None:
+            self.on_tick(self.tick - 1)
         self.outs = (aobs, arew, adone)
         self._called(adone.astype(bool))
 

@@ -55,9 +55,14 @@ __device__ __forceinline__ float clone_side(const Dev &d, float wa, int dt) {
   if (dt == 0) return wa;
   if (d.het) {
     const int b = __float_as_int(wa);
-    return side_pack((b >> ARCH_BITS) + dt, b & (TFX_MAX_ARCH - 1));
+    // (unsigned: a spawn tick below 2^24 plus a clock difference up to TFX_TICK_MAX passes INT32_MAX; only the low 24 bits count)
+    return side_pack((int)((unsigned)(b >> ARCH_BITS) + (unsigned)dt), b & (TFX_MAX_ARCH - 1));
   }
-  return wa + (float)dt;
+  // ONE rounding of spawn tick + dt, what a car spawned at that tick of the destination's clock holds ((float)tick).
+  // (float)dt is exact up to 2^24; past it wa + (float)dt would round twice - a clock difference of 2^31 - 2^20 is a
+  // multiple of 128 only by chance - and the sum of a float below 2^31 and an int32 is exact in binary64.
+  const float fd = (float)dt;
+  return (double)fd == (double)dt ? wa + fd : (float)((double)wa + (double)dt);
 }
 
 // words [0, n) of a per-env array, shared out over the env's G wavefronts

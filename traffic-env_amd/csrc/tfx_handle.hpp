@@ -136,6 +136,14 @@ struct tfx_handle_s {
   int ev_ticks = 0, ev_used = 0;
   std::vector<int> ev_weight;  // ticks the i-th timed entry covers (1, or the ticks of a fused launch)
   bool prof = false;
+  // The host's mirror of the device clock (tickA between calls): set by tfx_reset and tfx_set_tick, advanced
+  // by every call by the ticks it runs.  The device moves its clock by exactly that on every path - k_advance / k_tail
+  // add one / two per launch whatever the envs do (frozen envs skip their work, not the clock), the first half of a
+  // split call moves the handle's own words through the call's ticks and the second a copy of them (clock2,
+  // tfx_sequence.hpp), k_res adds n_ticks once (own_clock
+  // or k_tick_add), and a replayed graph holds the launches of the capture.  A call that fails half-way has moved the
+  // device clock by no more than the mirror: an upper bound then, which is all the domain check needs.
+  long long clock = 0;
   long long fused_ticks = 0;   // ticks run by k_res since tfx_create
   long long pair_ticks = 0;    // ticks run as two-tick passes since tfx_create
   long long tail_ticks = 0;    // ... of which k_tail finished the pair (tfx_tail.hpp)
@@ -252,5 +260,20 @@ int check_handle(tfx_handle h, bool need_bound) {
   if (need_bound && !h->bound) return fail(TFX_ESTATE, "tfx_bind_buffers has not been called");
   return TFX_OK;
 }
+
+// may a call run n more ticks?  The clock's domain is 0 .. TFX_TICK_MAX (include/tfx.h); checked before anything is enqueued
+int clock_room(tfx_handle h, long long n, const char *call) {
+  if (h->clock + n > (long long)TFX_TICK_MAX)
+    return fail(TFX_ESTATE, "%s: the clock stands at %lld and %lld more tick%s would take it past TFX_TICK_MAX = %d "
+                            "(tfx_set_tick or tfx_reset move it back)", call, h->clock, n, n == 1 ? "" : "s", TFX_TICK_MAX);
+  return TFX_OK;
+}
+
+// counts a call's ticks into the mirror when the call returns, however it returns
+struct ClockAdvance {
+  tfx_handle h;
+  long long n;
+  ~ClockAdvance() { h->clock += n; }
+};
 
 }  // namespace

@@ -125,6 +125,8 @@ extern "C" int tfx_agent_step(tfx_handle h, int32_t n_ticks, int32_t remi, float
   if (h->stream.upfront() && n_ticks > h->stream.rows)
     return fail(TFX_EINVAL, "n_ticks = %d: a decision's arrivals are drawn up front and the demand's count buffer holds %d "
                             "rows at this batch size", n_ticks, h->stream.rows);
+  if (int rc = clock_room(h, n_ticks, "tfx_agent_step")) return rc;
+  ClockAdvance advanced{h, n_ticks};
   hipStream_t st = (hipStream_t)stream;
   if (!res_usable(h, n_ticks)) {
     if (int rc = size_grids(h, true, n_ticks)) return rc;
@@ -631,6 +633,7 @@ int tfx_reset(tfx_handle h, const int32_t *phase_init, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipMemsetAsync(h->d.tickA, 0, sizeof(int), st));
   HIPCHK(hipMemsetAsync(h->d.tickB, 0, sizeof(int), st));
+  h->clock = 0;
   hipLaunchKernelGGL(k_reset, dim3(grid_for(h, (long)h->d.E * h->d.R)), dim3(256), 0, st, h->d, phase_init,
                      (const uint8_t *)nullptr, h->ep);
   HIPCHK(hipGetLastError());
@@ -705,7 +708,8 @@ int tfx_set_actions(tfx_handle h, int32_t mode, const int32_t *dev, int32_t peri
     return TFX_OK;
   }
   if (mode == TFX_ACTION_CYCLE) {
-    if (period < 1) return fail(TFX_EINVAL, "cycle period must be >= 1");
+    if (period < 1 || period > TFX_PERIOD_MAX)
+      return fail(TFX_EINVAL, "cycle period must be >= 1 and <= TFX_PERIOD_MAX = %d", TFX_PERIOD_MAX);
     d.action_period = period;
   } else if (mode == TFX_ACTION_BUFFER || mode == TFX_ACTION_BROADCAST) {
     if (!dev) return fail(TFX_EINVAL, "action buffer is null");
@@ -820,6 +824,8 @@ int tfx_demand_rows_per_road(tfx_handle h, int32_t *per_road) {
 int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
   if (n_ticks < 0) return fail(TFX_EINVAL, "n_ticks < 0");
+  if (int rc = clock_room(h, n_ticks, "tfx_step")) return rc;
+  ClockAdvance advanced{h, n_ticks};
   hipStream_t st = (hipStream_t)stream;
   // envs that fit a compute unit's LDS: all the ticks of the call in one launch (tfx_resident.hpp)
   if (n_ticks > 0 && res_usable(h, n_ticks)) {
@@ -851,6 +857,7 @@ int tfx_step(tfx_handle h, int32_t n_ticks, void *stream) {
 
 int tfx_move_cars(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
+  if (int rc = clock_room(h, 1, "tfx_move_cars")) return rc;  // (the advance that completes the tick moves the clock)
   if (int rc = size_grids(h, false, 1)) return rc;
   if (int rc = launch_greedy(h, (hipStream_t)stream)) return rc;
   // (rule 4: the row of the tick the clock stands at)
@@ -860,7 +867,9 @@ int tfx_move_cars(tfx_handle h, void *stream) {
 
 int tfx_advance_finished_cars(tfx_handle h, void *stream) {
   if (int rc = check_handle(h, true)) return rc;
+  if (int rc = clock_room(h, 1, "tfx_advance_finished_cars")) return rc;
   if (int rc = size_grids(h, false, 1)) return rc;
+  ClockAdvance advanced{h, 1};
   return launch_advance(h, 0, (hipStream_t)stream);
 }
 
@@ -900,9 +909,12 @@ int tfx_get_tick(tfx_handle h, int32_t *tick) {
 
 int tfx_set_tick(tfx_handle h, int32_t tick) {
   if (int rc = check_handle(h, false)) return rc;
+  if (tick < 0 || tick > TFX_TICK_MAX)
+    return fail(TFX_EINVAL, "tick %d is outside the clock's domain 0 .. TFX_TICK_MAX = %d", tick, TFX_TICK_MAX);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(h->d.tickA, &tick, sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->d.tickB, &tick, sizeof(int), hipMemcpyHostToDevice));
+  h->clock = tick;
   // tick stamps taken under the old clock must not alias ticks of the new one
   HIPCHK(hipMemset(h->d.env_flag, 0, (size_t)h->d.E * sizeof(int)));
   if (h->bound) HIPCHK(hipMemset(h->d.done_tick, 0, (size_t)h->d.E * sizeof(int)));

@@ -10,6 +10,9 @@ MAX_ARCH = 64
 ACTION_BUFFER, ACTION_BROADCAST, ACTION_CYCLE, ACTION_GREEDY = 0, 1, 2, 3
 SPAWN_NONE, SPAWN_COUNTS, SPAWN_PERIODIC = 0, 1, 2
 ABI_VERSION = 13
+EINVAL, ESTATE = -1, -2                 # TFX_EINVAL, TFX_ESTATE
+PERIOD_MAX = 1 << 20                    # TFX_PERIOD_MAX: the longest fixed light cycle
+TICK_MAX = 0x7fffffff - PERIOD_MAX      # TFX_TICK_MAX: the clock's domain is 0 .. TICK_MAX
 CLONE_STREAM, CLONE_EPISODE = 1, 2      # flags of tfx_clone_envs
 MEASURE_ACCUMULATE = 1                  # flag of tfx_road_measures
 CELLS_ACCUMULATE = 1                    # flag of tfx_road_cells

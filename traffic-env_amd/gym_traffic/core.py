@@ -1225,6 +1225,7 @@ class TfxEngine(object):
         set_actions / set_spawns.  Updates `done` (overflow in any of these ticks) unless the caller
         derives it from `done_tick` itself (update_done=False saves a launch)."""
         first = self.tick
+        self._clock_room(int(n_ticks), "step")
         self._epoch += 1
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_step(self.h, int(n_ticks), self._stream()))
@@ -1243,6 +1244,7 @@ class TfxEngine(object):
             self._arew = self._aout[na:].view(self.E, self.I)
             # the decision's done flags ARE the engine's `done` (what reset_done() defaults to)
             self._adone = self.done
+        self._clock_room(int(n_ticks), "agent_step")
         self._epoch += 1
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_agent_step(self.h, int(n_ticks), int(bool(remi)), _ptr(self._aobs),
@@ -1251,12 +1253,14 @@ class TfxEngine(object):
         return self._aobs, self._arew, self._adone
 
     def move_cars(self):
+        self._clock_room(1, "move_cars")
         self._epoch += 1
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_move_cars(self.h, self._stream()))
 
     def advance_finished_cars(self):
         first = self.tick
+        self._clock_room(1, "advance_finished_cars")
         self._epoch += 1
         with torch.cuda.device(self.device):
             nat.check(self.lib.tfx_advance_finished_cars(self.h, self._stream()))
@@ -1279,8 +1283,20 @@ class TfxEngine(object):
         return flat.reshape(self.E, 4, self.m, self.n).permute(0, 2, 3, 1)
 
     def set_tick(self, tick):
+        """The clock's domain is 0 .. nat.TICK_MAX (include/tfx.h); checked here as well: the C ABI takes an int32, and
+        ctypes would wrap a Python int that does not fit one."""
+        if not 0 <= int(tick) <= nat.TICK_MAX:
+            raise nat.TfxError("tfx error %d: tick %d is outside the clock's domain 0 .. TFX_TICK_MAX = %d"
+                               % (nat.EINVAL, int(tick), nat.TICK_MAX))
         nat.check(self.lib.tfx_set_tick(self.h, int(tick)))
         self.tick = int(tick)
+
+    def _clock_room(self, n, call):
+        """the handle's own check (csrc/tfx_handle.hpp:clock_room) on the mirror `tick`: nothing is enqueued, nothing
+        changes when a call would run a tick past the clock's domain"""
+        if self.tick + n > nat.TICK_MAX:
+            raise nat.TfxError("tfx error %d: %s: the clock stands at %d and %d more tick(s) would take it past "
+                               "TFX_TICK_MAX = %d (set_tick or reset move it back)" % (nat.ESTATE, call, self.tick, n, nat.TICK_MAX))
 
     def vehicle_updates(self):
         out = C.c_uint64()

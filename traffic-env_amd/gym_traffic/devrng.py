@@ -369,7 +369,8 @@ def put_cars(x, v, w, arch, leading, lastcar, C, offsets, xv, row, spawn, env_id
     max(0, min(base + run, cap) - first); the road then holds n = min(fit, C - 2) cars, car j in slot wrap(leading' + 1 + j)
     from entry first + j; leading' = new_leading[key] where that lies in 1 .. C-1, otherwise the road's own; lastcar' the
     slot of car n - 1, leading' when n == 0; slot leading' shows lead_x[key]; lost sums run - n.  The spawn tick becomes
-    spawn + spawn_shift (heterogeneous handles, het: int(spawn) + spawn_shift modulo 2^24, the row modulo 64)."""
+    float32(spawn + spawn_shift), the exact sum rounded once (heterogeneous handles, het: int(spawn) + spawn_shift modulo
+    2^24, the row modulo 64)."""
     C = int(C)
     x, v = np.array(x, np.float32), np.array(v, np.float32)
     E, R = x.shape[0], x.shape[1]
@@ -406,7 +407,10 @@ def put_cars(x, v, w, arch, leading, lastcar, C, offsets, xv, row, spawn, env_id
                 if het:
                     w[env, rd, slot] = ((tk.astype(np.int64) + shift) & 0xFFFFFF).astype(np.float32)
                 else:
-                    w[env, rd, slot] = tk if shift == 0 else tk + np.float32(shift)
+                    # (one rounding of the sum: a shift float32 does not hold is added in binary64, csrc/tfx_clone.hpp)
+                    exact = float(np.float32(shift)) == float(shift)
+                    w[env, rd, slot] = tk if shift == 0 else tk + np.float32(shift) if exact else \
+                        (tk.astype(np.float64) + float(shift)).astype(np.float32)
             if arch is not None:
                 arch[env, rd, slot] = 0 if row is None else np.asarray(row, np.uint8).reshape(-1)[take] & 63
             x[env, rd, l] = np.inf if lead_x is None else np.asarray(lead_x, np.float32).reshape(-1)[key]
