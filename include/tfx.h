@@ -990,6 +990,68 @@ int tfx_put_cars(tfx_handle h, const int32_t *env_ids /*device, NULL: selection 
                  int32_t flags, void *stream);
 /* Test support: the launch geometry tfx_put_cars uses for this handle and n_sel chosen envs, like tfx_car_list_launch. */
 int tfx_put_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves);
+/* State digests on the device: a 64-bit fingerprint per chosen env, and optionally one per road, from one read-only
+ * launch over the live cars (k_digest, csrc/tfx_digest.hpp).  "Are these two env states the same bits?" as 8 bytes per
+ * env: a check of what tfx_clone_envs, tfx_put_cars or a sharded run claim, for every env at once; a transposition key
+ * for tree search.  A FINGERPRINT, NOT A CRYPTOGRAPHIC HASH: equal states always give equal digests; unequal states give
+ * different digests except by accident (about 2^-64 per pair of unrelated states), and an adversary can construct
+ * collisions.
+ *
+ * Definition, integer arithmetic only, on the image tfx_export_ring would produce at that moment (on a ring-layout handle:
+ * on xv itself) and on the bound buffers - so it is also defined between two-tick passes, after a clone, between
+ * tfx_move_cars and tfx_advance_finished_cars, and it is equal across layouts, shardings and handles.  All arithmetic is
+ * uint64 modulo 2^64.
+ *   mix(z)     the splitmix64 finaliser, in this order: z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27;
+ *              z *= 0x94d049bb133111eb; z ^= z >> 31.
+ *   G          0x9e3779b97f4a7c15.
+ *   Parts      `parts` is a non-zero sum of the TFX_DIGEST_* bits below and nothing else:
+ *     CARS   = 1   the count and every car's (x, v) bit patterns
+ *     ROWS   = 2   every car's archetype row, as tfx_car_list gives `row` (0 on single-archetype handles)
+ *     SPAWN  = 4   every car's spawn tick: the bit pattern of the float tfx_car_list gives in `spawn`; handles with
+ *                  planes == 3 only, else TFX_EINVAL
+ *     RING   = 8   `leading` of every road (the wrapped-ring branch of the model makes the ring position part of what
+ *                  the next tick depends on)
+ *     LIGHTS = 16  current_phase[I] and elapsed[I] from obs
+ *     OBS    = 32  passed[r], detected[r], waiting[r], passed_dst[I], the bit patterns of rewards[I], done_tick
+ *   Selection  env_ids holds n_sel env numbers (NULL: selection s is env s, n_sel <= E); repeats are allowed.
+ *   Per road   For road e of a shown env whose road_mask byte is non-zero (NULL: every road), with n the count as
+ *              tfx_cars_on_roads clamps it and car j the j-th from the head in ring order - tfx_car_list's order:
+ *                A_j = xbits | vbits << 32,   B_j = spawnbits | row << 32   (a half of B_j is 0 where its part is off)
+ *                road = mix(1 + n)
+ *                     + [RING]           mix((2 << 56) | leading)
+ *                     + [CARS]           sum over j of mix(A_j + (2j + 1) * G)
+ *                     + [ROWS or SPAWN]  sum over j of mix(B_j + (2j + 2) * G)
+ *              With none of CARS, ROWS, SPAWN and RING set no road term enters the env digest at all, road_digest is 0
+ *              and no car row is loaded.  Float bit patterns are hashed as they are: -0.0 differs from 0.0, NaNs differ
+ *              by payload.
+ *   Per word   Sections s = 1 current_phase, 2 elapsed (LIGHTS), 3 passed, 4 detected, 5 waiting, 6 passed_dst,
+ *              7 rewards, 8 done_tick (OBS): index i and 32-bit value val give mix((s << 56) | (i << 32) | val); a uint8
+ *              is zero-extended, an int32 or a float contributes its bit pattern.
+ *   Per env    env = sum over the unmasked roads e of mix(road_e + (e + 1) * G) + the word terms of the chosen sections.
+ *              road_digest[s][e] = road_e, 0 for masked-out roads.  A selection whose id lies outside [0, E) has env = 0
+ *              and every road_digest = 0; nothing of the handle's state is read for it.
+ * Every combination is a sum, so any evaluation order gives the same bits.  Spawn ticks are clock-relative: compare envs
+ * taken at different clocks without SPAWN (done_tick, inside OBS, is a clock stamp too where it is not 0).  What only the
+ * handle owns - caches, arrival-stream positions, episode accounting - is not caller-visible state and is not hashed.
+ *
+ * One memset of env_digest and one launch on `stream`, no host synchronisation; nothing in the handle or in the caller's
+ * bound state is written: captured step / agent-step graphs stay valid, and tfx_debug_fail_after does not count the
+ * launch.  TFX_MEASURE_GRID and TFX_GRID_CAP cap the launch as they cap the measures'.  TFX_EINVAL: a NULL handle or
+ * env_digest, n_sel <= 0, n_sel > E with env_ids NULL, n_sel * R beyond int32, parts 0 or with unknown bits, SPAWN on a
+ * planes == 2 handle, flags other than 0; TFX_ESTATE before tfx_bind_buffers.  A refused call launches nothing.
+ * gym_traffic/devrng.py state_digest states the definition in NumPy. */
+#define TFX_DIGEST_CARS 1
+#define TFX_DIGEST_ROWS 2
+#define TFX_DIGEST_SPAWN 4
+#define TFX_DIGEST_RING 8
+#define TFX_DIGEST_LIGHTS 16
+#define TFX_DIGEST_OBS 32
+int tfx_state_digest(tfx_handle h, const int32_t *env_ids /*device, NULL: selection s is env s*/, int32_t n_sel,
+                     const uint8_t *road_mask /*device [R] or NULL*/, int32_t parts,
+                     uint64_t *env_digest /*device [n_sel], required*/, uint64_t *road_digest /*device [n_sel][R] or NULL*/,
+                     int32_t flags /*0*/, void *stream);
+/* Test support: the launch geometry tfx_state_digest uses for this handle and n_sel chosen envs, like tfx_car_list_launch. */
+int tfx_digest_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves);
 /* Test support: out (HOST uint8 [E][R]) receives, per road, the rows at the top of its column that hold no car - what a
  * two-tick pass leaves between calls on the transposed layout (0 everywhere on the ring layout).  Synchronises the stream. */
 int tfx_debug_head_rows(tfx_handle h, uint8_t *out, void *stream);

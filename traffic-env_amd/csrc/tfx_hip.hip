@@ -24,6 +24,7 @@
 #include "tfx_follow.hpp"
 #include "tfx_ends.hpp"
 #include "tfx_cars.hpp"
+#include "tfx_digest.hpp"
 #include "tfx_put.hpp"
 #include "tfx_frames.hpp"
 #include "tfx_clone.hpp"
@@ -1344,6 +1345,51 @@ int tfx_put_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves) {
   if (int rc = check_handle(h, false)) return rc;
   if (int rc = car_list_sel_ok(h, n_sel)) return rc;
   return report_launch(tile_grid(h, false, n_sel), grid, waves);
+}
+
+// the n_sel of the two digest calls: at least one selection, and road words s * R + road id that fit an int32
+static int digest_sel_ok(tfx_handle h, int32_t n_sel) {
+  if (n_sel < 1) return fail(TFX_EINVAL, "digest: n_sel %d is less than 1", n_sel);
+  if ((long long)n_sel * h->d.R > 0x7fffffffll)
+    return fail(TFX_EINVAL, "digest: %d selections of %d roads do not fit int32", n_sel, h->d.R);
+  return TFX_OK;
+}
+
+int tfx_state_digest(tfx_handle h, const int32_t *env_ids, int32_t n_sel, const uint8_t *road_mask, int32_t parts,
+                     uint64_t *env_digest, uint64_t *road_digest, int32_t flags, void *stream) {
+  // (the arguments first, as tfx_road_cells checks them: each cause is named whatever state the handle is in)
+  if (!env_digest) return fail(TFX_EINVAL, "digest: env_digest is null");
+  if (flags) return fail(TFX_EINVAL, "unknown digest flags 0x%x", flags);
+  if (parts == 0 || (parts & ~DG_ALL_PARTS)) return fail(TFX_EINVAL, "digest: parts 0x%x is empty or has unknown bits", parts);
+  if (int rc = check_handle(h, false)) return rc;
+  if (int rc = digest_sel_ok(h, n_sel)) return rc;
+  if (!env_ids && n_sel > h->d.E)
+    return fail(TFX_EINVAL, "digest: n_sel %d is more than the handle's %d envs and env_ids is null", n_sel, h->d.E);
+  if ((parts & TFX_DIGEST_SPAWN) && h->cfg.planes != 3)
+    return fail(TFX_EINVAL, "digest: the handle carries no side plane (planes == 2): spawn ticks are not kept");
+  if (int rc = check_handle(h, true)) return rc;
+  DigestArgs a{};
+  a.env_ids = env_ids;
+  a.road_mask = road_mask;
+  a.n_sel = n_sel;
+  a.parts = parts;
+  a.env_digest = reinterpret_cast<unsigned long long *>(env_digest);
+  a.road_digest = reinterpret_cast<unsigned long long *>(road_digest);
+  // the env words are sums of the wavefronts' shares: they start at 0, as tfx_frames' background starts white
+  HIPCHK(hipMemsetAsync(env_digest, 0, (size_t)n_sel * sizeof(uint64_t), (hipStream_t)stream));
+  // k_cars' launch: (selected env, tile) items.  The walk by the parts (tfx_digest.hpp)
+  const bool cars = (parts & TFX_DIGEST_CARS) != 0, bword = (parts & (TFX_DIGEST_ROWS | TFX_DIGEST_SPAWN)) != 0;
+  const long grid = tile_grid(h, true, n_sel);
+  if (cars && bword) return launch_query(k_digest<2>, grid, stream, h->d, a);
+  if (cars) return launch_query(k_digest<1>, grid, stream, h->d, a);
+  if (bword) return launch_query(k_digest<3>, grid, stream, h->d, a);
+  return launch_query(k_digest<0>, grid, stream, h->d, a);
+}
+
+int tfx_digest_launch(tfx_handle h, int32_t n_sel, int32_t *grid, int32_t *waves) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (int rc = digest_sel_ok(h, n_sel)) return rc;
+  return report_launch(tile_grid(h, true, n_sel), grid, waves);
 }
 
 int tfx_car_ages(tfx_handle h, const tfx_age_buffers *out, int32_t flags, void *stream) {

@@ -25,6 +25,9 @@ MAX_HEADS = 16                          # TFX_MAX_HEADS: the most cars tfx_road_
 ENDS_NO_CAR = 255                       # TFX_ENDS_NO_CAR: the row of a padded entry
 FRAME_PX_MIN, FRAME_PX_MAX = 8, 256     # TFX_FRAME_PX_MIN, TFX_FRAME_PX_MAX
 DEMAND_MAX_PROFILES, DEMAND_MAX_SEGMENTS, DEMAND_MAX_CDF = 16, 64, 256   # limits of tfx_set_demand
+# TFX_DIGEST_*: the parts of tfx_state_digest
+DIGEST_CARS, DIGEST_ROWS, DIGEST_SPAWN, DIGEST_RING, DIGEST_LIGHTS, DIGEST_OBS = 1, 2, 4, 8, 16, 32
+DIGEST_ALL = 63
 
 
 class TfxConfig(C.Structure):
@@ -188,6 +191,9 @@ _PROTOS = {
     "tfx_put_cars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                C.POINTER(TfxPutBuffers), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "tfx_put_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tfx_state_digest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_void_p]),
+    "tfx_digest_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

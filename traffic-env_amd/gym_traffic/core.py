@@ -666,6 +666,60 @@ class TfxEngine(object):
         tests)."""
         return self._launch_report(self.lib.tfx_car_list_launch, int(n_sel))
 
+    def digest_parts(self):
+        """every TFX_DIGEST_* part this engine has: all of them, without SPAWN where there is no side plane (planes == 2)
+        and without ROWS where there is no archetype table (every row is 0)"""
+        parts = nat.DIGEST_CARS | nat.DIGEST_RING | nat.DIGEST_LIGHTS | nat.DIGEST_OBS
+        if self.het:
+            parts |= nat.DIGEST_ROWS
+        if self.P == 3:
+            parts |= nat.DIGEST_SPAWN
+        return parts
+
+    def state_digest(self, envs=None, parts=None, roads=None, per_road=False, out=None):
+        """A 64-bit fingerprint of the state of chosen envs, from one read-only launch over their live cars
+        (tfx_state_digest, include/tfx.h, which states the rule; gym_traffic.devrng.state_digest is the definition in
+        NumPy) -> int64 [n_sel] device tensor holding the bits of the uint64 digests; per_road=True: (env, road int64
+        [n_sel, R]), a digest per road id as well.  Two envs - of this engine or of any other, whatever its layout, E
+        or sharding - whose chosen parts hold the same bits have equal digests; a fingerprint, not a cryptographic hash.
+        envs: a list, an array or an int32 device tensor of env numbers (None: every env in order; repeats are fine; an id
+        outside [0, E) gives 0); parts: a sum of nat.DIGEST_CARS | ROWS | SPAWN | RING | LIGHTS | OBS (None: every part
+        this engine has, digest_parts()); roads: a uint8 / bool mask [R] by road id (None: every road; a masked-out road
+        enters no digest and its road word is 0).  out: the caller's int64 tensor [n_sel], or with per_road the pair
+        (env, road); default: tensors the engine keeps per (n_sel, per_road) and reuses - clone() what must last.  No
+        host synchronisation when envs is None or a device tensor; nothing of the env state is written."""
+        ids, n_sel = self._env_ids(envs)
+        if n_sel < 1:
+            raise ValueError("state_digest: no env chosen")
+        parts = self.digest_parts() if parts is None else int(parts)
+        if parts <= 0 or parts & ~nat.DIGEST_ALL:
+            raise ValueError("state_digest: parts 0x%x is empty or has unknown bits" % parts)
+        if parts & nat.DIGEST_SPAWN and self.P != 3:
+            raise ValueError("state_digest: DIGEST_SPAWN needs the spawn plane (planes == 3: validate mode or heterogeneous cars)")
+        mask = self._road_mask(roads, "state_digest")
+        key = ("state_digest", (n_sel, bool(per_road)))
+        if out is None:
+            out = self._planes.get(key)
+            if out is None:
+                out = self._planes[key] = (
+                    torch.zeros((n_sel,), dtype=torch.int64, device=self.device),
+                    torch.zeros((n_sel, self.R), dtype=torch.int64, device=self.device) if per_road else None)
+            env, road = out
+        else:
+            env, road = tuple(out) if per_road else (out, None)
+            if not _is_plane(env, torch.int64, (n_sel,)) or (per_road and not _is_plane(road, torch.int64, (n_sel, self.R))):
+                raise ValueError("state_digest(out=): contiguous int64 device tensors [%d]%s are needed"
+                                 % (n_sel, " and [%d, %d]" % (n_sel, self.R) if per_road else ""))
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.tfx_state_digest(self.h, _ptr(ids), n_sel, _ptr(mask), parts, _ptr(env), _ptr(road), 0,
+                                                self._stream()))
+        return (env, road) if per_road else env
+
+    def digest_launch(self, n_sel):
+        """(workgroups, wavefronts) of the state_digest launch of this engine for n_sel chosen envs (tfx_digest_launch;
+        tests)."""
+        return self._launch_report(self.lib.tfx_digest_launch, int(n_sel))
+
     def _dev(self, who, a, dtype, np_dtype, shape, what):
         """argument `what` of method `who` - a caller's tensor or array-like - as a contiguous device tensor of this dtype
         and shape (None stays None)"""

@@ -419,6 +419,108 @@ def put_cars(x, v, w, arch, leading, lastcar, C, offsets, xv, row, spawn, env_id
     return x, v, w, arch, ld.astype(np.int32), lc.astype(np.int32), lost
 
 
+DIGEST_CARS, DIGEST_ROWS, DIGEST_SPAWN, DIGEST_RING, DIGEST_LIGHTS, DIGEST_OBS = 1, 2, 4, 8, 16, 32
+DIGEST_G = np.uint64(0x9e3779b97f4a7c15)
+
+
+def digest_mix(z):
+    """the splitmix64 finaliser over a uint64 array (modulo 2^64; integer arrays wrap without a warning)"""
+    z = np.array(z, np.uint64)
+    z ^= z >> np.uint64(30)
+    z *= np.uint64(0xbf58476d1ce4e5b9)
+    z ^= z >> np.uint64(27)
+    z *= np.uint64(0x94d049bb133111eb)
+    z ^= z >> np.uint64(31)
+    return z
+
+
+def _bits32(a, dtype):
+    """the 32-bit patterns of an array of `dtype` (float32 / int32: as they are; uint8: zero-extended) as uint64"""
+    a = np.ascontiguousarray(np.asarray(a, dtype))
+    return (a if dtype == np.uint8 else a.view(np.uint32)).astype(np.uint64)
+
+
+def state_digest(x, v, w, arch, leading, lastcar, C, flags, env_ids=None, road_mask=None, obs=None, rewards=None,
+                 waiting=None, passed_dst=None, done_tick=None, I=None, r=None):
+    """The definition of tfx_state_digest (include/tfx.h) in NumPy, over ring planes and car_list's ordering: x, v float32
+    [E, R, C] by ring slot (what tfx_export_ring produces), w float32 [E, R, C] the spawn ticks, arch uint8 [E, R, C] the
+    archetype rows (None: every row is 0), leading / lastcar int [E, R]; flags: a non-zero sum of DIGEST_CARS | ROWS |
+    SPAWN | RING | LIGHTS | OBS.  env_ids: n_sel env numbers (None: every env in order; repeats allowed; an id outside
+    [0, E) gives 0 everywhere); road_mask uint8 [R] or None (a road with mask 0 enters no digest, its road word is 0).
+    LIGHTS and OBS read obs int32 [E, 2r + 2I] (passed | detected | current_phase | elapsed) with I and r given; OBS also
+    rewards float32 [E, I], waiting int32 [E, r], passed_dst uint8 [E, I], done_tick int32 [E].  An array whose part is off
+    is not read: pass None.  -> uint64 (env [n_sel], road [n_sel, R]).
+    All arithmetic is uint64 modulo 2^64; mix = digest_mix, G = DIGEST_G.  With n the clamped ring count of a road and car
+    j the j-th from its head in ring order, A_j = xbits | vbits << 32, B_j = spawnbits | row << 32 (a half is 0 where its
+    part is off):  road = mix(1 + n) + [RING] mix(2 << 56 | leading) + [CARS] sum_j mix(A_j + (2j + 1) G) + [ROWS or
+    SPAWN] sum_j mix(B_j + (2j + 2) G);  env = sum over unmasked roads e of mix(road_e + (e + 1) G) + the word terms
+    mix(s << 56 | i << 32 | val) of sections s = 1 current_phase, 2 elapsed (LIGHTS), 3 passed, 4 detected, 5 waiting,
+    6 passed_dst, 7 rewards, 8 done_tick (OBS).  With none of CARS, ROWS, SPAWN, RING no road term enters and road is 0."""
+    flags = int(flags)
+    if flags <= 0 or flags & ~63:
+        raise ValueError("state_digest: flags 0x%x is empty or has unknown bits" % flags)
+    u64 = np.uint64
+    ld = np.asarray(leading, np.int64)
+    E, R = ld.shape
+    ids = np.arange(E, dtype=np.int64) if env_ids is None else np.asarray(env_ids, np.int64).reshape(-1)
+    n_sel = len(ids)
+    shown = (ids >= 0) & (ids < E)
+    env = np.where(shown, ids, 0)
+    mask = np.ones(R, bool) if road_mask is None else np.asarray(road_mask).reshape(R) != 0
+    live = shown[:, None] & mask[None, :]                     # [n_sel, R]: roads that enter
+    road = np.zeros((n_sel, R), u64)
+    env_d = np.zeros(n_sel, u64)
+    cars, rows, spawn = flags & DIGEST_CARS, flags & DIGEST_ROWS, flags & DIGEST_SPAWN
+    if flags & (DIGEST_CARS | DIGEST_ROWS | DIGEST_SPAWN | DIGEST_RING):
+        if spawn and w is None:
+            raise ValueError("state_digest: DIGEST_SPAWN needs the spawn plane w")
+        if cars:
+            xs, vs = x, v
+        else:       # car_list wants the shapes only
+            xs = vs = np.zeros(ld.shape + (int(C),), np.float32)
+        N, offsets, xv, key, row, sp = car_list(xs, vs, w if spawn else None, arch if rows else None, leading, lastcar, C,
+                                                env_ids=ids, road_mask=road_mask)
+        off = offsets.astype(np.int64)
+        n = (off[1:] - off[:-1]).reshape(n_sel, R)            # clamped counts, 0 where masked or not shown
+        road = digest_mix(u64(1) + n.astype(u64))
+        if flags & DIGEST_RING:
+            road += digest_mix((u64(2) << u64(56)) | (ld[env] & 0xFFFFFFFF).astype(u64))
+        j = (np.arange(N) - off[key]).astype(u64)             # every listed car's place from the head
+        if cars:
+            a = _bits32(xv[:, 0], np.float32) | (_bits32(xv[:, 1], np.float32) << u64(32))
+            np.add.at(road.reshape(-1), key, digest_mix(a + (u64(2) * j + u64(1)) * DIGEST_G))
+        if rows or spawn:
+            b = np.zeros(N, u64)
+            if spawn:
+                b |= _bits32(sp, np.float32)
+            if rows:
+                b |= row.astype(u64) << u64(32)
+            np.add.at(road.reshape(-1), key, digest_mix(b + (u64(2) * j + u64(2)) * DIGEST_G))
+        road = np.where(live, road, u64(0))
+        e1 = (np.arange(R, dtype=u64) + u64(1)) * DIGEST_G
+        env_d += np.where(live, digest_mix(road + e1[None, :]), u64(0)).sum(axis=1, dtype=u64)
+
+    def words(s, vals):     # the terms of section s over vals [n_sel, count] of 32-bit patterns
+        i = np.arange(vals.shape[1], dtype=u64)[None, :]
+        t = digest_mix((u64(s) << u64(56)) | (i << u64(32)) | vals)
+        return np.where(shown, t.sum(axis=1, dtype=u64), u64(0))
+
+    if flags & (DIGEST_LIGHTS | DIGEST_OBS):
+        if obs is None or I is None or r is None:
+            raise ValueError("state_digest: DIGEST_LIGHTS / DIGEST_OBS need obs, I and r")
+        I, r = int(I), int(r)
+        ob = _bits32(np.asarray(obs).reshape(E, 2 * r + 2 * I)[env], np.int32)
+        if flags & DIGEST_LIGHTS:
+            env_d += words(1, ob[:, 2 * r:2 * r + I]) + words(2, ob[:, 2 * r + I:])
+        if flags & DIGEST_OBS:
+            env_d += words(3, ob[:, :r]) + words(4, ob[:, r:2 * r])
+            env_d += words(5, _bits32(np.asarray(waiting).reshape(E, r)[env], np.int32))
+            env_d += words(6, _bits32(np.asarray(passed_dst).reshape(E, I)[env], np.uint8))
+            env_d += words(7, _bits32(np.asarray(rewards).reshape(E, I)[env], np.float32))
+            env_d += words(8, _bits32(np.asarray(done_tick).reshape(E, 1)[env], np.int32))
+    return env_d, road
+
+
 def car_ages(w, leading, lastcar, C, now, het=False):
     """The definition of tfx_car_ages (include/tfx.h) in NumPy, over the ring plane w float32 [..., R, C] of spawn ticks
     by ring slot (what tfx_export_ring produces; heterogeneous handles: the spawn tick modulo 2^24), leading / lastcar

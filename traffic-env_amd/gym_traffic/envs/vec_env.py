@@ -654,6 +654,60 @@ class TrafficVecEnv(object):
         if self._travel is not None and eng.n_trips is not None:
             self._travel["cursor"][idx] = eng.n_trips[idx]
 
+    # ---- state digests (tfx_state_digest, include/tfx.h) -----------------------------------------------------------
+    def digest_parts(self, parts='state'):
+        """The TFX_DIGEST_* bits of a named set (an int passes through):
+            'cars'   CARS | ROWS - the cars alone: counts, (x, v) bits and archetype rows, wherever the ring stands
+            'state'  CARS | ROWS | RING | LIGHTS | OBS - everything the next tick depends on that a caller can see, except
+                     the clock-relative spawn ticks.  The next tick reads `detected` (through the observation), and the
+                     library hands out the counters as ONE part, so 'state' takes OBS whole: passed, waiting, passed_dst,
+                     rewards and done_tick ride along.  Two envs that differ only in those accumulated counters are
+                     different under 'state'; done_tick is a clock stamp where an env has overflowed (0 otherwise)
+            'all'    'state' plus SPAWN, where the envs keep spawn ticks (validate or heterogeneous): equal only at the
+                     same clock, spawn ticks are absolute
+        ROWS is dropped where there is no archetype table (every row is 0 there)."""
+        from gym_traffic import _native as nat
+        if not isinstance(parts, str):
+            return int(parts)
+        eng = self.engine
+        rows = nat.DIGEST_ROWS if eng.het else 0
+        state = nat.DIGEST_CARS | rows | nat.DIGEST_RING | nat.DIGEST_LIGHTS | nat.DIGEST_OBS
+        sets = dict(cars=nat.DIGEST_CARS | rows, state=state, all=state | (nat.DIGEST_SPAWN if eng.P == 3 else 0))
+        if parts not in sets:
+            raise ValueError("digest: parts must be 'cars', 'state', 'all' or a sum of DIGEST_* bits, not %r" % (parts,))
+        return sets[parts]
+
+    def digest(self, envs=None, parts='state', per_road=False):
+        """A 64-bit fingerprint of every chosen env's state, on the device, with no host synchronisation: one read-only
+        launch over the live cars (TfxEngine.state_digest / tfx_state_digest, include/tfx.h) -> int64 [len(envs)] device
+        tensor (the uint64 bits); per_road=True: (env, road int64 [len(envs), R]).  Envs whose chosen parts hold the same
+        bits have equal digests - within this batch, across batches, layouts, shards and snapshots: a transposition key
+        for tree search, an 8-byte-per-env check of a sharded run.  A fingerprint, not a cryptographic hash.  envs: a
+        list, an array or an int32 device tensor of env numbers (None: every env); parts: see digest_parts.  The engine
+        keeps one tensor per (len(envs), per_road): the next such call overwrites it - clone() what must last."""
+        return self.engine.state_digest(envs, parts=self.digest_parts(parts), per_road=per_road)
+
+    def same_state(self, src_of_env, source=None, parts='state'):
+        """bool [E] device tensor: entry e is True iff env e's digest equals that of env src_of_env[e] of `source`
+        (another TrafficVecEnv of the same world; default: this one) - the argument shape of clone_envs, so
+        `same_state(idx)` after `clone_envs(idx)` checks the clone for every env at once.  -1 (or any index outside the
+        source) gives False.  Two launches, no host synchronisation when src_of_env is a device tensor."""
+        other = self if source is None else source
+        eng = self.engine
+        idx = src_of_env if isinstance(src_of_env, torch.Tensor) else torch.as_tensor(np.asarray(src_of_env, np.int32))
+        idx = idx.to(device=eng.device, dtype=torch.int32).reshape(-1).contiguous()
+        if idx.numel() != eng.E:
+            raise ValueError("src_of_env must hold one index per env (%d), got %d" % (eng.E, idx.numel()))
+        bits = self.digest_parts(parts)
+        if bits != other.digest_parts(parts):
+            raise ValueError("same_state: the two envs do not have the same parts for %r" % (parts,))
+        mine = torch.empty((eng.E,), dtype=torch.int64, device=eng.device)
+        theirs = torch.empty((eng.E,), dtype=torch.int64, device=other.engine.device)
+        eng.state_digest(None, parts=bits, out=mine)
+        other.engine.state_digest(idx.to(other.engine.device), parts=bits, out=theirs)
+        ok = (idx >= 0) & (idx < other.num_envs)
+        return ok & (mine == theirs.to(eng.device))
+
     def arterial(self, row_or_col, direction):
         """uint8 [R] road mask of one arterial: the chain of roads a car of `direction` (0 eastbound, 1 westbound - along
         row `row_or_col`; 2 towards higher rows, 3 towards lower rows - along column `row_or_col`) drives through, from
